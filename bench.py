@@ -3,14 +3,17 @@
 all-reduce + SGD step) of CABiNet-MobileNetV3-Large with the hand-written HIP CAB / FFM
 kernels, on N MI355X of one node (BASELINE.json metric, config 3 per GPU / config 4 at N=8).
 
-    python bench.py --gpus 1 --steps 20 --warmup 5
+    python bench.py --gpus 1 --steps 20 --warmup 5 [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with two extra objects:
-``roofline`` (dominant hand-written kernel: algorithmic FLOPs / measured launch duration vs the
-gfx950 dense fp32-MFMA peak) and ``cpu_baseline`` (the CPU oracle timed on this host, N=1 only),
-plus ``kernels`` (every hand-written kernel group with its own roofline numbers).
+Prints ONE JSON line on rank 0 (contract in the task statement).  A plain run sets up, warms up,
+times the K steps and prints the line; ``--dump-outputs DIR`` also writes what the last timed step
+computed (see dump_outputs).  ``--full`` adds, after the timed steps, ``fwd_loss_bwd_only`` (the
+steps without the SGD update), ``eval_forward``, ``roofline`` (dominant hand-written kernel:
+algorithmic FLOPs / measured launch duration vs the gfx950 dense fp32-MFMA peak), ``kernels``
+(every hand-written kernel group with its own roofline numbers), ``hot_path_ms_per_step`` and
+``cpu_baseline`` (the CPU oracle timed on this host, N=1 only).
 """
 
 from __future__ import annotations
@@ -53,12 +56,22 @@ if os.path.isdir(_MIOPEN_DB) and "MIOPEN_USER_DB_PATH" not in os.environ:
     try:
         _tmp = tempfile.mkdtemp(prefix="cabinet_miopen_")
         _db = os.path.join(_tmp, "db")
-        shutil.copytree(_MIOPEN_DB, _db)
+        # plain file copies, then owner-writable directories: a checkout with read-only modes must not give MIOpen a read-only
+        # user database or kernel cache (copytree's default copy2 / copystat would carry the modes over)
+        shutil.copytree(_MIOPEN_DB, _db, copy_function=shutil.copyfile)
+        for _dir, _, _ in os.walk(_db):
+            os.chmod(_dir, 0o700)
         atexit.register(shutil.rmtree, _tmp, ignore_errors=True)
         os.environ["MIOPEN_USER_DB_PATH"] = _db
         os.environ.setdefault("MIOPEN_CUSTOM_CACHE_DIR", os.path.join(_db, "cache"))
     except OSError:
         pass
+# FAST find mode, as the test session runs MIOpen (tests/conftest.py): a problem with a record in the database above takes the
+# recorded solver -- the choice the default mode makes from the same record, so the timed step is unchanged where the records
+# apply -- and a problem without one takes MIOpen's heuristic choice instead of timing solvers on the spot.  On a clean checkout on
+# another MI355X the default mode's first step ended in miopenStatusInternalError inside a stock convolution of the spatial branch,
+# while the test session, in FAST mode, passed on the same machine.
+os.environ.setdefault("MIOPEN_FIND_MODE", "FAST")
 
 import torch  # noqa: E402
 
@@ -97,7 +110,15 @@ def parse():
                     "running statistics, full-resolution logits) instead of the training step; one JSON line of its own")
     ap.add_argument("--no-eval-forward", action="store_true", help="skip the forward-only measurement that the training line carries "
                     "as `eval_forward`")
+    ap.add_argument("--full", action="store_true", help="after the timed steps also measure what the headline figure does not need: "
+                    "the steps without the SGD update (`fwd_loss_bwd_only`), the eval-mode forward (`eval_forward`), the per-kernel "
+                    "rooflines (`kernels`, `roofline`, `hot_path_ms_per_step`) and the CPU baseline (`cpu_baseline`); the --no-* "
+                    "switches above and --all-kernels / --kernel-iters / --cpu-batch act on these")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps write what the last timed step "
+                    "left its caller (loss, gradients, parameters, BatchNorm running statistics) as DIR/<name>.npy")
     args = ap.parse_args()
+    if args.dump_outputs and (args.eval or args.kernels_only):
+        ap.error("--dump-outputs writes the outputs of the timed training step: not with --eval or --kernels-only")
     args.height = args.height or args.size
     args.width = args.width or args.size
     return args
@@ -541,7 +562,7 @@ def time_eval_forward(net, im, steps, warmup):
             stop.record()
             torch.cuda.synchronize()
             res["graph_ms"] = start.elapsed_time(stop) / steps
-            # not bitwise: bench.py leaves MIOpen its default solvers, and some of the backbone's convolutions sum with atomics
+            # not bitwise: bench.py does not ask MIOpen for deterministic solvers, and some of the backbone's convolutions sum with atomics
             res["graph_vs_eager_rel"] = float((s_out.double() - out.double()).norm() / out.double().norm().clamp_min(1e-30))
             del graph
         except Exception as e:  # noqa: BLE001
@@ -587,6 +608,42 @@ def eval_line(args, net, im, dev):
     if k1:
         out["cab_attn_fwd"] = {k: k1[0][k] for k in ("kernel", "ms_per_launch", "bound", "achieved", "peak", "unit", "frac")}
     return out
+
+
+DUMP_BUDGET_BYTES = 60 * 2 ** 20   # all files of --dump-outputs together stay below 64 MB, .npy headers included
+DUMP_SAMPLE_SEED = 0
+
+
+def dump_outputs(out_dir, net, loss):
+    """`--dump-outputs DIR`: what the last timed step left its caller, for comparing two builds output for output.
+
+    loss.npy              float64 (1,)  the step's loss
+    grads.npy             float32       every trainable parameter's gradient, flattened and concatenated in named_parameters order
+    bn_running_stats.npy  float32       every floating-point buffer (BatchNorm running mean / var) after the step, same order rule
+    params.npy            float32       the parameters after the SGD update; when all of them would not fit in the budget beside
+                                        the files above, a fixed sample: the sorted first k indices of a randperm seeded with
+                                        DUMP_SAMPLE_SEED over the concatenated parameters (the same indices for every build)
+
+    The inputs are seeded, but bench.py does not ask MIOpen for deterministic solvers, and some of its choices sum with atomics: two runs
+    of ONE build at config 3 gave the same loss bit for bit, gradients 3.4e-3 apart (||a - b|| / ||b||), running statistics
+    2e-7 and parameters 4e-8 apart on an MI355X.  A comparison of two builds needs tolerances above that floor."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    with torch.no_grad():
+        grads = torch.cat([(p.grad if p.grad is not None else torch.zeros_like(p)).reshape(-1).float()
+                           for p in net.parameters() if p.requires_grad]).cpu()
+        stats = torch.cat([b.reshape(-1).float() for b in net.buffers() if b.is_floating_point()]).cpu()
+        params = torch.cat([p.reshape(-1).float() for p in net.parameters()]).cpu()
+    arrays = {"loss": np.array([float(loss)], dtype=np.float64), "grads": grads.numpy(), "bn_running_stats": stats.numpy()}
+    room = max(0, DUMP_BUDGET_BYTES - sum(a.nbytes for a in arrays.values())) // params.element_size()
+    if params.numel() > room:
+        idx = torch.randperm(params.numel(), generator=torch.Generator().manual_seed(DUMP_SAMPLE_SEED))[:room].sort().values
+        params = params[idx]
+    arrays["params"] = params.numpy()
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, f"{name}.npy"), a)
+    return {name: list(a.shape) for name, a in arrays.items()}
 
 
 def main():
@@ -684,27 +741,31 @@ def main():
         dt = max(float(x) for x in every)
     final_loss = float(loss)
     log(f"timed region {dt:.3f}s -> {world * args.batch * args.steps / dt:.2f} images/s")
-    # SURVEY.md section 8(d) words the metric as forward + 2x OHEM-CE + backward; `value` above also contains the gradient
-    # all-reduce and the SGD step (conservative).  The same K steps without the optimizer, reported next to it:
-    def set_optimizer(o):  # the optimizer step is not part of any captured graph: same step, segment skipped
-        step.optimizer = o
-        if hasattr(step, "opt_seg"):
-            step.opt_seg.optimizer = o
-        if hasattr(step, "eager"):
-            step.eager.optimizer = o
+    if args.dump_outputs and rank == 0:
+        shapes = dump_outputs(args.dump_outputs, net, loss)
+        log(f"outputs of the last timed step written to {args.dump_outputs}: {shapes}")
+    if args.full:
+        # SURVEY.md section 8(d) words the metric as forward + 2x OHEM-CE + backward; `value` above also contains the gradient
+        # all-reduce and the SGD step (conservative).  The same K steps without the optimizer, reported next to it:
+        def set_optimizer(o):  # the optimizer step is not part of any captured graph: same step, segment skipped
+            step.optimizer = o
+            if hasattr(step, "opt_seg"):
+                step.opt_seg.optimizer = o
+            if hasattr(step, "eager"):
+                step.eager.optimizer = o
 
-    set_optimizer(None)
-    sync()
-    t0 = time.perf_counter()
-    for _ in range(args.steps):
-        step(im, lb)
-    sync()
-    dt_nopt = time.perf_counter() - t0
-    set_optimizer(opt)
-    if ddp:
-        t = torch.tensor([dt_nopt], device=dev, dtype=torch.float64)
-        torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
-        dt_nopt = float(t)
+        set_optimizer(None)
+        sync()
+        t0 = time.perf_counter()
+        for _ in range(args.steps):
+            step(im, lb)
+        sync()
+        dt_nopt = time.perf_counter() - t0
+        set_optimizer(opt)
+        if ddp:
+            t = torch.tensor([dt_nopt], device=dev, dtype=torch.float64)
+            torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
+            dt_nopt = float(t)
 
     result = None
     if rank == 0:
@@ -736,16 +797,19 @@ def main():
                                           "all": [round(x, 3) for x in per_rank_ms]} if per_rank_ms else None),
                 "ddp_schedule": getattr(step, "schedule", None) if ddp else None,
                 "cpu_affinity": ddp_mod.AFFINITY if world > 1 else None,
+                "miopen_find_mode": os.environ.get("MIOPEN_FIND_MODE"),
             },
             "library": {"source_digest": _build.source_digest()[:16], "fresh": _build.is_fresh(),
                         "what": "sha256 of cabinet_amd/csrc/* + include/cabinet_hip.h; the loaded libcabinet_hip.so carries this stamp"},
             "final_loss": round(final_loss, 5),
-            "fwd_loss_bwd_only": {"value": round(images / dt_nopt, 3), "unit": "images/s",
-                                  "ms_per_step": round(dt_nopt / args.steps * 1e3, 3),
-                                  "what": "the same K steps without the SGD step (forward + 2x OHEM-CE + backward"
-                                          + (" + gradient all-reduce)" if ddp else ")")},
         }
-    if rank == 0 and world == 1 and not args.no_eval_forward:
+        if args.full:
+            result["fwd_loss_bwd_only"] = {"value": round(images / dt_nopt, 3), "unit": "images/s",
+                                           "ms_per_step": round(dt_nopt / args.steps * 1e3, 3),
+                                           "what": "the same K steps without the SGD step (forward + 2x OHEM-CE + backward"
+                                                   + (" + gradient all-reduce)" if ddp else ")")}
+    # ---- everything below measures more than the headline figure needs: only with --full -----------------------------------------
+    if rank == 0 and world == 1 and args.full and not args.no_eval_forward:
         # the forward-only path of evaluate.py:77 on the model that was just timed (its BatchNorm running statistics have seen
         # warmup + steps batches): .eval() + no_grad, full-resolution logits; `python bench.py --eval` prints
         # this as a line of its own
@@ -758,7 +822,7 @@ def main():
                                           "same forward through the Python dispatch"}
         log(f"eval forward: {ms:.2f} ms/batch graphed, {r['eager_ms']:.2f} eager")
     # ---- per-kernel rooflines and CPU baseline: rank 0, outside the timed region -----------------
-    if rank == 0 and not args.no_kernel_roofline:
+    if rank == 0 and args.full and not args.no_kernel_roofline:
         del step, opt
         torch.cuda.empty_cache()
         ks = kernel_rooflines(args.batch, args.height, args.width, args.classes, args.kernel_iters, args.all_kernels)
@@ -806,7 +870,7 @@ def main():
                                                                              "unit", "frac", "traffic", "algorithmic_gflop")}
     if ddp:
         torch.distributed.barrier()
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         from oracle import model_ref
         sd = {k: v.detach().cpu() for k, v in net.state_dict().items()}
         cb = model_ref.time_cpu_baseline(sd, args.mode, args.cpu_batch, (args.height, args.width), args.classes)

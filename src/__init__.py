@@ -7,7 +7,7 @@ reference src/scripts/train.py:19, evaluate.py:18) resolves to the MI355X-native
 (train.py:18-31).  ``pkgutil.extend_path`` appends every other ``src/`` directory on ``sys.path`` to this
 package's search path: modules that exist here (``src.models.{cab,cabinet,constants,mobilenetv3}``,
 ``src.utils.loss``) win because this repo comes first, every other ``src.*`` module resolves to the reference.
-``tests/test_reference_drives_it.py`` runs the reference's unmodified ``train_and_evaluate`` this way."""
+``tests/test_reference_drives_it.py`` checks this resolution."""
 from pkgutil import extend_path
 
 __path__ = extend_path(__path__, __name__)

@@ -23,7 +23,11 @@ if os.path.isdir(_MIOPEN_DB) and "MIOPEN_USER_DB_PATH" not in os.environ:
     try:
         _tmp = tempfile.mkdtemp(prefix="cabinet_miopen_tests_")
         _db = os.path.join(_tmp, "db")
-        shutil.copytree(_MIOPEN_DB, _db)
+        # as bench.py copies it: plain file copies and owner-writable directories, so that a checkout with read-only modes does not
+        # hand MIOpen a read-only user database or kernel cache
+        shutil.copytree(_MIOPEN_DB, _db, copy_function=shutil.copyfile)
+        for _dir, _, _ in os.walk(_db):
+            os.chmod(_dir, 0o700)
         atexit.register(shutil.rmtree, _tmp, ignore_errors=True)
         os.environ["MIOPEN_USER_DB_PATH"] = _db
         os.environ.setdefault("MIOPEN_CUSTOM_CACHE_DIR", os.path.join(_db, "cache"))
@@ -56,7 +60,7 @@ def pytest_collection_modifyitems(config, items):
         # gradient upstream (216 of 221 tensors move; gamma.grad lands up to 1.9e-3 from the reference's value), depends on the
         # run.  With torch.backends.cudnn.deterministic (MIOPEN_CONVOLUTION_ATTRIB_DETERMINISTIC on every descriptor) six repeats are
         # bit-identical in every logit and every gradient: the verdict of the parity suite no longer depends on box history.
-        # (bench.py keeps MIOpen's default choice: the timed step is what a user runs.)
+        # (bench.py takes the database copy and FAST find mode, but not the deterministic solvers.)
         torch.backends.cudnn.deterministic = True
         return
     skip = pytest.mark.skip(reason="no GPU in this process")

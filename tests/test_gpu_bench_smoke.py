@@ -1,5 +1,5 @@
 """bench.py's per-kernel roofline loop at a tiny size: every kernel group must launch and report finite numbers
-(the default `python bench.py` runs this loop at config 3 after the timed region)."""
+(`python bench.py --full` runs this loop at config 3 after the timed region)."""
 import importlib.util
 import json
 import math
@@ -114,8 +114,8 @@ def test_bench_main_with_two_ranks_on_one_gpu():
 @pytest.mark.timeout(900)
 def test_bench_eval_line_and_training_line_fields():
     """`bench.py --eval` (round 6): the forward-only path evaluate.py:77 consumes -- .eval(), no_grad, BatchNorm on
-    running statistics, full-resolution logits -- as a JSON line of its own; and the training line's round-6 fields at a small size:
-    `eval_forward`, `hot_path_ms_per_step` (the section-8 groups the step launches, once each), `library` (digest of the sources the
+    running statistics, full-resolution logits -- as a JSON line of its own; and the fields of the `--full` training line at a small
+    size: `fwd_loss_bwd_only`, `eval_forward`, `hot_path_ms_per_step` (the section-8 groups the step launches, once each), `library` (digest of the sources the
     loaded library was built from), both roofs per matrix group."""
     env = dict(os.environ)
     env.pop("MIOPEN_USER_DB_PATH", None)
@@ -129,9 +129,10 @@ def test_bench_eval_line_and_training_line_fields():
     assert e["forward"]["finite"] and e["forward"]["out_shape"] == [2, 8, 256, 256]
     assert e["forward"]["graph_ms"] is None or e["forward"]["graph_vs_eager_rel"] < 1e-4
     assert e["roofline"]["kernel"].startswith("ffm_up_fwd_eval") and "evaluate.py:77" in e["config"]["workload"]
-    out = subprocess.run(base, env=env, capture_output=True, text=True, timeout=800, cwd=ROOT)
+    out = subprocess.run(base + ["--full"], env=env, capture_output=True, text=True, timeout=800, cwd=ROOT)
     assert out.returncode == 0, (out.stdout[-2000:], out.stderr[-4000:])
     r = json.loads([ln for ln in out.stdout.splitlines() if ln.strip()][-1])
+    assert r["fwd_loss_bwd_only"]["ms_per_step"] > 0
     assert r["eval_forward"]["value"] > 0 and r["eval_forward"]["ms_per_step"] > 0
     hp = r["hot_path_ms_per_step"]
     assert 0 < hp["value"] and 0 < hp["share_of_step"] and "conv3x3_out_fwd" in hp["groups"] and "cab_attn_fwd_bf16x6" not in hp["groups"]
@@ -139,3 +140,37 @@ def test_bench_eval_line_and_training_line_fields():
     assert r["library"]["fresh"] is True
     ffm = [k for k in r["kernels"] if k["kernel"].startswith(("ffm_up_fwd ", "ffm_up_bwd "))]
     assert len(ffm) == 2 and all("frac_mfma" in k and "frac_hbm" in k and k["frac"] == max(k["frac_mfma"], k["frac_hbm"]) for k in ffm)
+
+
+@pytest.mark.timeout(900)
+def test_bench_plain_run_is_lean_and_dumps_the_last_steps_outputs(tmp_path):
+    """A plain run (no --full) prints the headline line without the measurements it does not need; --dump-outputs writes what the
+    last timed step left its caller -- loss, gradients, BatchNorm running statistics, the updated parameters (a seeded sample when
+    the Large model's do not fit beside its gradients) -- as float .npy files within 64 MB."""
+    import numpy as np
+
+    from cabinet_amd.train import build_model
+
+    env = dict(os.environ)
+    env.pop("MIOPEN_USER_DB_PATH", None)
+    env.pop("MIOPEN_CUSTOM_CACHE_DIR", None)
+    dump = tmp_path / "outputs"
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "2", "--batch", "2", "--size", "256",
+           "--dump-outputs", str(dump)]
+    out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=800, cwd=ROOT)
+    assert out.returncode == 0, (out.stdout[-2000:], out.stderr[-4000:])
+    lines = [ln for ln in out.stdout.splitlines() if ln.strip()]
+    assert sum(ln.lstrip().startswith("{") for ln in lines) == 1
+    r = json.loads(lines[-1])
+    assert r["steps"] == 3 and r["warmup"] == 2 and r["unit"] == "images/s" and r["higher_is_better"] is True and r["dtype"] == "f32"
+    assert r["ms_per_step"] > 0 and abs(r["value"] - 2 * 3 / (r["ms_per_step"] * 3e-3)) < 1e-2 * r["value"]
+    assert not set(r) & {"fwd_loss_bwd_only", "eval_forward", "kernels", "roofline", "hot_path_ms_per_step", "cpu_baseline"}
+    assert r["config"]["miopen_find_mode"] == "FAST"
+    files = {p.stem: np.load(p) for p in dump.glob("*.npy")}
+    assert set(files) == {"loss", "grads", "bn_running_stats", "params"}
+    assert sum(p.stat().st_size for p in dump.glob("*.npy")) <= 64 * 10 ** 6
+    assert all(a.dtype in (np.float32, np.float64) and np.isfinite(a).all() for a in files.values())
+    assert abs(float(files["loss"][0]) - r["final_loss"]) < 1e-4
+    net = build_model("large", n_classes=8)
+    assert files["grads"].size == sum(p.numel() for p in net.parameters() if p.requires_grad) and np.abs(files["grads"]).max() > 0
+    assert 0 < files["params"].size < sum(p.numel() for p in net.parameters())

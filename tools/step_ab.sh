@@ -6,7 +6,7 @@ cd $GRAFT_REPO_ROOT
 for rep in 1 2 3 4; do
   for val in default 0; do
     if [ $val = default ]; then unset $V; else export $V=$val; fi
-    python bench.py --steps 200 --warmup 20 --no-cpu-baseline --no-kernel-roofline --no-eval-forward 2>/dev/null | python -c "
+    python bench.py --full --steps 200 --warmup 20 --no-cpu-baseline --no-kernel-roofline --no-eval-forward 2>/dev/null | python -c "
 import json,sys; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('$V=$val', d['ms_per_step'], 'ms/step', d['value'], 'images/s;  fwd+loss+bwd only:', d['fwd_loss_bwd_only']['ms_per_step'], 'ms')" >> $OUT
     unset $V
   done
