@@ -140,6 +140,14 @@ hipError_t conv3x3_fwd_run(const WinoShape& s, const float* x0, const float* x1,
                            hipStream_t stream);
 hipError_t conv3x3_bwd_run(const WinoShape& s, const float* dy, const float* x0, const float* x1, const float* w, float* dx0,
                            float* dx1, float* dw, void* ws, hipStream_t stream);
+// eval_tail.hip
+int eval_chip_threads(int C, int wl, int cw, int nsrc);
+hipError_t eval_chip_accum_run(const float* a, const float* b, int N, int C, int hl, int wl, int ch, int cw, float* dst, int FH,
+                               int FW, int y0, int x0, const float* rcp_y, const float* rcp_x, hipStream_t stream);
+hipError_t eval_scale_merge_run(const float* prob, int N, int C, int FH, int FW, int hst, int hed, int wst, int wed, float* total,
+                                int H, int W, hipStream_t stream);
+hipError_t eval_argmax_hist_run(const float* total, const long long* labels, int N, int C, int H, int W, int ignore_lb, long long* hist,
+                                unsigned char* pred, hipStream_t stream);
 }  // namespace cabinet
 
 static thread_local char g_err[512] = "";
@@ -1067,6 +1075,52 @@ int cabinet_conv3x3_bwd(const float* dy, const float* x0, const float* x1, const
     return hip_status(cabinet::conv3x3_bwd_run(s, dy, x0, C1 > 0 ? x1 : nullptr, w, dx0, C1 > 0 ? dx1 : nullptr, dw, workspace,
                                                static_cast<hipStream_t>(stream)),
                       "conv3x3_bwd launch");
+}
+
+// ------------------------------------------------------------------ evaluation tail (K13)
+int cabinet_eval_chip_accum_supported(int C, int hl, int wl, int ch, int cw, int flip) {
+    if (C < 1 || C > 32 || hl < 1 || wl < 1 || ch < 1 || cw < 1 || ch > 65535) return 0;
+    return cabinet::eval_chip_threads(C, wl, cw, flip ? 2 : 1) > 0 ? 1 : 0;
+}
+
+int cabinet_eval_chip_accum(const float* a, const float* b, int N, int C, int hl, int wl, int ch, int cw, float* dst, int FH, int FW,
+                            int y0, int x0, const float* rcp_y, const float* rcp_x, cabinet_stream_t stream) {
+    if (N <= 0 || C <= 0 || hl <= 0 || wl <= 0 || ch <= 0 || cw <= 0 || FH <= 0 || FW <= 0)
+        return fail(CABINET_ERR_INVALID_ARG, "eval_chip_accum: non-positive dimension");
+    if (!a || !dst) return fail(CABINET_ERR_INVALID_ARG, "eval_chip_accum: null tensor pointer");
+    if (y0 < 0 || x0 < 0 || y0 > FH - ch || x0 > FW - cw)
+        return fail(CABINET_ERR_INVALID_ARG, "eval_chip_accum: window (%d,%d)+(%d,%d) leaves the %dx%d destination", y0, x0, ch, cw, FH, FW);
+    if (C > 32) return fail(CABINET_ERR_UNSUPPORTED, "eval_chip_accum: C=%d classes (max 32)", C);
+    if (N > 65535 || ch > 65535) return fail(CABINET_ERR_UNSUPPORTED, "eval_chip_accum: N or chip height exceeds grid limits");
+    if (!cabinet_eval_chip_accum_supported(C, hl, wl, ch, cw, b != nullptr))
+        return fail(CABINET_ERR_UNSUPPORTED, "eval_chip_accum: C=%d x resize ratio %d/%d exceeds the LDS row buffers", C, wl, cw);
+    return hip_status(cabinet::eval_chip_accum_run(a, b, N, C, hl, wl, ch, cw, dst, FH, FW, y0, x0, rcp_y, rcp_x,
+                                                   static_cast<hipStream_t>(stream)),
+                      "eval_chip_accum launch");
+}
+
+int cabinet_eval_scale_merge(const float* prob, int N, int C, int FH, int FW, int hst, int hed, int wst, int wed, float* total, int H,
+                             int W, cabinet_stream_t stream) {
+    if (N <= 0 || C <= 0 || FH <= 0 || FW <= 0 || H <= 0 || W <= 0)
+        return fail(CABINET_ERR_INVALID_ARG, "eval_scale_merge: non-positive dimension");
+    if (!prob || !total) return fail(CABINET_ERR_INVALID_ARG, "eval_scale_merge: null tensor pointer");
+    if (hst < 0 || wst < 0 || hed <= hst || wed <= wst || hed > FH || wed > FW)
+        return fail(CABINET_ERR_INVALID_ARG, "eval_scale_merge: crop [%d:%d, %d:%d] leaves the %dx%d source", hst, hed, wst, wed, FH, FW);
+    if ((long long)N * C > 65535 || H > 65535) return fail(CABINET_ERR_UNSUPPORTED, "eval_scale_merge: N*C or H exceeds grid limits");
+    CABINET_REQUIRE_ALIGNED("eval_scale_merge", total);
+    return hip_status(cabinet::eval_scale_merge_run(prob, N, C, FH, FW, hst, hed, wst, wed, total, H, W, static_cast<hipStream_t>(stream)),
+                      "eval_scale_merge launch");
+}
+
+int cabinet_eval_argmax_hist(const float* total, const long long* labels, int N, int C, int H, int W, int ignore_lb, long long* hist,
+                             unsigned char* pred, cabinet_stream_t stream) {
+    if (N <= 0 || C <= 0 || H <= 0 || W <= 0) return fail(CABINET_ERR_INVALID_ARG, "eval_argmax_hist: non-positive dimension");
+    if (!total || !labels || !hist) return fail(CABINET_ERR_INVALID_ARG, "eval_argmax_hist: null tensor pointer");
+    if (C > 32) return fail(CABINET_ERR_UNSUPPORTED, "eval_argmax_hist: C=%d classes (max 32)", C);
+    CABINET_REQUIRE_ALIGNED("eval_argmax_hist", total, labels);
+    if (reinterpret_cast<uintptr_t>(pred) & 3) return fail(CABINET_ERR_INVALID_ARG, "eval_argmax_hist: pred must be 4-byte aligned");
+    return hip_status(cabinet::eval_argmax_hist_run(total, labels, N, C, H, W, ignore_lb, hist, pred, static_cast<hipStream_t>(stream)),
+                      "eval_argmax_hist launch");
 }
 
 }  // extern "C"

@@ -9,6 +9,8 @@
 ``dwconv`` / ``bn_act_dwconv``   mobilenetv3.py:118-126,135-143           (K8)
 ``stem_conv``       cabinet.py:111                                        (K9)     ``pwconv``   mobilenetv3.py:128-131
 OHEM head           src/utils/loss.py:51-80 + cabinet.py:240-245          (``ohem_up_*``, used by cabinet_amd.loss)
+evaluation tail     src/scripts/evaluate.py:69-159, :193-226              (K13: ``eval_chip_accum`` / ``eval_scale_merge`` /
+                    ``eval_argmax_hist``, no autograd; used by cabinet_amd.evaluate)
 
 ONE dispatch rule for every operator here:
   * device tensor, shape inside the kernel family's coverage (each family exports ``*_supported``): the hand-written
@@ -1400,3 +1402,94 @@ def pwconv(x, conv):
     if not x.is_cuda:
         raise RuntimeError("pwconv: device tensors only")
     return _PwConv.apply(x, conv.weight)
+
+
+# --------------------------------------------------------------------------- evaluation tail (K13; no autograd)
+
+
+def eval_chip_accum_supported(logits, chip_size, flip=False):
+    """True when the fused softmax + window accumulation takes these chip logits: a device tensor, at most 32 classes, and the
+    source rows of one segment of chip pixels fit the LDS (every model-resolution-to-chip ratio <= 1 does)."""
+    if not (logits.is_cuda and logits.dim() == 4 and _lib.available()):
+        return False
+    _, C, hl, wl = logits.shape
+    return bool(_lib.load().cabinet_eval_chip_accum_supported(C, hl, wl, int(chip_size[0]), int(chip_size[1]), int(bool(flip))))
+
+
+def eval_chip_accum(dst, logits, logits_flipped, chip_size, origin, rcp_y=None, rcp_x=None):
+    """dst[:, :, y0:y0+ch, x0:x0+cw] += rcp_y (x) rcp_x * mean over {chip, flipped chip} of softmax(upsample(logits -> chip_size))
+    -- reference evaluate.py:75-87 with the model's final upsample, and :133-137.  ``logits_flipped`` (or None) holds the logits
+    of the horizontally flipped chip; ``rcp_y`` (FH) / ``rcp_x`` (FW) the reciprocal window counts per row / column of ``dst``
+    (None: ones).  In place on ``dst`` (N, C, FH, FW), which must be dense fp32."""
+    lib = _lib.load()
+    if not (dst.is_cuda and dst.dtype == torch.float32 and dst.is_contiguous()):
+        raise RuntimeError("eval_chip_accum: dst must be a dense fp32 device tensor")
+    a = _f32c(logits)
+    b = _f32c(logits_flipped) if logits_flipped is not None else None
+    if b is not None and b.shape != a.shape:
+        raise RuntimeError("eval_chip_accum: the flipped chip's logits must have the shape of the chip's")
+    N, C, hl, wl = a.shape
+    if dst.shape[:2] != (N, C):
+        raise RuntimeError(f"eval_chip_accum: dst {tuple(dst.shape)} does not match logits {tuple(a.shape)}")
+    FH, FW = dst.shape[2:]
+    ry = _f32c(rcp_y) if rcp_y is not None else None
+    rx = _f32c(rcp_x) if rcp_x is not None else None
+    if (ry is not None and ry.numel() != FH) or (rx is not None and rx.numel() != FW):
+        raise RuntimeError("eval_chip_accum: rcp_y / rcp_x must have one entry per row / column of dst")
+    dev = dst.device
+    with torch.cuda.device(dev):
+        rc = lib.cabinet_eval_chip_accum(_ptr(a), _ptr(b), N, C, hl, wl, int(chip_size[0]), int(chip_size[1]), _ptr(dst), FH, FW,
+                                         int(origin[0]), int(origin[1]), _ptr(ry), _ptr(rx), _stream_handle(dev))
+    _lib.check(rc, "cabinet_eval_chip_accum")
+    return dst
+
+
+def eval_scale_merge_supported(total):
+    return bool(total.is_cuda and total.dim() == 4 and _lib.available() and total.shape[0] * total.shape[1] <= 65535
+                and total.shape[2] <= 65535)
+
+
+def eval_scale_merge(total, prob, crop=None):
+    """total += F.interpolate(prob[:, :, hst:hed, wst:wed], total.shape[2:], mode="bilinear", align_corners=False) in one pass
+    (reference evaluate.py:140-142, :156-158, :217).  ``crop`` = (hst, hed, wst, wed), None: all of ``prob``.  In place."""
+    lib = _lib.load()
+    if not (total.is_cuda and total.dtype == torch.float32 and total.is_contiguous()):
+        raise RuntimeError("eval_scale_merge: total must be a dense fp32 device tensor")
+    prob = _f32c(prob)
+    N, C, H, W = total.shape
+    if prob.shape[:2] != (N, C):
+        raise RuntimeError(f"eval_scale_merge: prob {tuple(prob.shape)} does not match total {tuple(total.shape)}")
+    FH, FW = prob.shape[2:]
+    hst, hed, wst, wed = crop if crop is not None else (0, FH, 0, FW)
+    dev = total.device
+    with torch.cuda.device(dev):
+        rc = lib.cabinet_eval_scale_merge(_ptr(prob), N, C, FH, FW, int(hst), int(hed), int(wst), int(wed), _ptr(total), H, W,
+                                          _stream_handle(dev))
+    _lib.check(rc, "cabinet_eval_scale_merge")
+    return total
+
+
+def eval_argmax_hist_supported(total):
+    return bool(total.is_cuda and total.dim() == 4 and _lib.available() and total.shape[1] <= 32)
+
+
+def eval_argmax_hist(total, labels, hist, ignore_label, want_pred=False):
+    """hist[argmax_c total, clip(label)] += 1 over the pixels whose label != ignore_label (reference evaluate.py:218-224 with
+    compute_hist, :161-191).  ``labels`` (N, H, W) int64 on the device; ``hist`` (C, C) int64 on the device, updated in place
+    with integer atomics.  Returns the (N, H, W) uint8 predictions when ``want_pred``."""
+    lib = _lib.load()
+    if not (total.is_cuda and total.dtype == torch.float32 and total.is_contiguous()):
+        raise RuntimeError("eval_argmax_hist: total must be a dense fp32 device tensor")
+    N, C, H, W = total.shape
+    if labels.dtype != torch.int64 or tuple(labels.shape) != (N, H, W) or labels.device != total.device:
+        raise RuntimeError("eval_argmax_hist: labels must be (N, H, W) int64 on total's device")
+    if hist.dtype != torch.int64 or tuple(hist.shape) != (C, C) or not hist.is_contiguous() or hist.device != total.device:
+        raise RuntimeError("eval_argmax_hist: hist must be a dense (C, C) int64 tensor on total's device")
+    labels = _aligned(labels)
+    pred = torch.empty((N, H, W), dtype=torch.uint8, device=total.device) if want_pred else None
+    dev = total.device
+    with torch.cuda.device(dev):
+        rc = lib.cabinet_eval_argmax_hist(_ptr(total), _ptr(labels), N, C, H, W, int(ignore_label), _ptr(hist), _ptr(pred),
+                                          _stream_handle(dev))
+    _lib.check(rc, "cabinet_eval_argmax_hist")
+    return pred

@@ -37,7 +37,7 @@
 extern "C" {
 #endif
 
-#define CABINET_ABI_VERSION 7
+#define CABINET_ABI_VERSION 8
 
 #define CABINET_OK 0
 #define CABINET_ERR_INVALID_ARG (-1) /* null pointer, non-positive dim            */
@@ -485,6 +485,36 @@ size_t cabinet_conv3x3_bwd_workspace_bytes(int B, int C0, int C1, int Co, int H,
 int cabinet_conv3x3_bwd(const float* dy, const float* x0, const float* x1, const float* w, int B, int C0, int C1, int Co,
                         int H, int W, float* dx0, float* dx1, float* dw,
                         void* workspace, size_t workspace_bytes, cabinet_stream_t stream);
+
+/* ------------------------------------------------------------------------- *
+ * Evaluation tail (ABI v8): everything the multi-scale evaluator does after the model, on the device.
+ * Replaces src/scripts/evaluate.py:75-87 (eval_chip: softmax, flip, softmax, +=, *= 0.5) together with the final x8
+ * upsample of cabinet.py:240-245, :133-134 (window +=, count +=), :137 (prob / count), :156-158 (resize back) with :217
+ * (probs +=), and :218-224 with :161-191 (argmax, copy to the host, numpy.bincount per image).
+ *
+ * cabinet_eval_chip_accum -- one launch per chip.
+ *   a (N,C,hl,wl): logits of the chip at the model's resolution; b: same shape, logits of the horizontally flipped chip,
+ *   or NULL (no flip).  For every pixel (y,x) of the ch x cw chip: the C logits sampled bilinearly from `a`
+ *   (align_corners=False, ratios hl/ch and wl/cw, PyTorch's source-index rule; exact at ratio 1), softmax over classes;
+ *   with b the same at column cw-1-x of b's upsample and the two averaged; the result times rcp_y[y0+y] * rcp_x[x0+x]
+ *   is ADDED to dst (N,C,FH,FW) at (y0+y, x0+x).  rcp_y (FH) and rcp_x (FW) hold 1 / (number of windows covering the row /
+ *   the column): the reference's count map is their outer product and never exists; NULL = all ones.
+ *   Launches that write overlapping windows must be ordered on one stream (plain read-modify-write, no atomics).
+ *   C <= 32 (8 and 19 are compiled forms); supported when the staged source rows fit the LDS (any ratio <= 1 does).
+ * cabinet_eval_scale_merge -- total (N,C,H,W) += resize(prob (N,C,FH,FW)[:, :, hst:hed, wst:wed] -> (H,W)), bilinear,
+ *   align_corners=False; prob is already normalised by the reciprocals above.
+ * cabinet_eval_argmax_hist -- pred = argmax over C of total (N,C,H,W), lowest index on ties; labels (N,H,W) int64;
+ *   a pixel whose label == ignore_lb is dropped, any other label is clipped into [0, C-1];
+ *   hist (C,C) int64, hist[pred][label] += 1 (integer atomics: exactly reproducible; the caller zeroes it once);
+ *   pred (N,H,W) uint8 receives the predictions when not NULL.  C <= 32.
+ * ------------------------------------------------------------------------- */
+int cabinet_eval_chip_accum_supported(int C, int hl, int wl, int ch, int cw, int flip);
+int cabinet_eval_chip_accum(const float* a, const float* b, int N, int C, int hl, int wl, int ch, int cw, float* dst, int FH, int FW,
+                            int y0, int x0, const float* rcp_y, const float* rcp_x, cabinet_stream_t stream);
+int cabinet_eval_scale_merge(const float* prob, int N, int C, int FH, int FW, int hst, int hed, int wst, int wed, float* total, int H,
+                             int W, cabinet_stream_t stream);
+int cabinet_eval_argmax_hist(const float* total, const long long* labels, int N, int C, int H, int W, int ignore_lb, long long* hist,
+                             unsigned char* pred, cabinet_stream_t stream);
 
 #ifdef __cplusplus
 }
