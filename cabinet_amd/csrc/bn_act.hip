@@ -253,7 +253,144 @@ __global__ void gate_act_dgate_kernel(const float* __restrict__ part, int rows, 
     dgate[row] = s;
 }
 
+// ---- backward of the squeeze-excite tail as one operator: y = act(g[b,c] * x), x = gamma * xhat + beta = bn(z),
+// g = SE-MLP(avgpool(x)) (reference mobilenetv3.py:146-149 with SELayer :68-83; the forward is K7 + the pool + the MLP +
+// gate_act_fwd, unchanged).  Composed from the separate backward operators this is gate_act_bwd (read dy, x; write dx),
+// the pool's broadcast gradient (write), autograd's add of the two (read 2, write 1), then BatchNorm's reduce (read 2) and
+// dx (read 2, write 1).  Here: 2 reads of (dy, z) + 1 write, and x is never kept for backward:
+//   reduce : A[b,c] = sum_p du, X[b,c] = sum_p du * xhat, S[b,c] = sum_p xhat, du = dy * act'(u), u = g * x
+//            -> dgate = gamma X + beta A; the MLP backward (torch, on (B, C)) gives ds, the pooled input's gradient
+//   dx     : dz = gamma invstd (g du + ds/P - sum(dx)/N - xhat sum(dx xhat)/N)   (eval mode: without the two means),
+//            sum(dx) = sum_b (g A + ds), sum(dx xhat) = sum_b (g X + ds S / P) per channel
+
+// part[k][row][chunk], k = 0: sum du, 1: sum du * xhat, 2: sum xhat
+__global__ __launch_bounds__(BA_T) void se_bwd_reduce_kernel(const float* __restrict__ dy, const float* __restrict__ z,
+                                                             const float* __restrict__ mean, const float* __restrict__ invstd,
+                                                             const float* __restrict__ weight, const float* __restrict__ bias,
+                                                             const float* __restrict__ gate, int rows, int C, int P, int chunks,
+                                                             int act, float* __restrict__ part) {
+    __shared__ float red[4];
+    const int row = blockIdx.x / chunks, ch = blockIdx.x - row * chunks, c = row % C;
+    const float mu = mean[c], inv = invstd[c], gam = weight[c], bet = bias[c], gt = gate[row];
+    f32x4 vz[BA_V], vg[BA_V];
+    ba_load(z + (size_t)row * P, P, ch * BA_CHUNK, vz);
+    ba_load(dy + (size_t)row * P, P, ch * BA_CHUNK, vg);  // zeros past the end: no contribution
+    float s1 = 0.f, s2 = 0.f, s3 = 0.f;
+#pragma unroll
+    for (int i = 0; i < BA_V; ++i)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const float xh = (vz[i][e] - mu) * inv;
+            const float du = vg[i][e] * act_grad(fmaf(xh, gam, bet) * gt, act);
+            s1 += du, s2 = fmaf(du, xh, s2);
+            if (ba_valid(P, ch * BA_CHUNK, i, e)) s3 += xh;
+        }
+    s1 = block_sum_256(s1, red);
+    s2 = block_sum_256(s2, red);
+    s3 = block_sum_256(s3, red);
+    if (threadIdx.x == 0) {
+        part[(size_t)row * chunks + ch] = s1;
+        part[((size_t)rows + row) * chunks + ch] = s2;
+        part[((size_t)2 * rows + row) * chunks + ch] = s3;
+    }
+}
+
+// per row (b,c): sums[k][row] = A, X, S (the chunks of the row in order) and the gradient at the hard sigmoid's input,
+// da2 = dgate / 6 where 0 < a2 + 3 < 6 (autograd's ReLU6 convention), dgate = gamma X + beta A
+__global__ void se_bwd_gate_kernel(const float* __restrict__ part, int rows, int C, int chunks, const float* __restrict__ weight,
+                                   const float* __restrict__ bias, const float* __restrict__ a2, float* __restrict__ sums,
+                                   float* __restrict__ da2) {
+    const int row = blockIdx.x * blockDim.x + threadIdx.x;
+    if (row >= rows) return;
+    float s[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        float t = 0.f;
+        for (int j = 0; j < chunks; ++j) t += part[((size_t)k * rows + row) * chunks + j];
+        sums[(size_t)k * rows + row] = s[k] = t;
+    }
+    const int c = row % C;
+    const float dgate = weight[c] * s[1] + bias[c] * s[0], u = a2[row] + 3.f;
+    da2[row] = (u > 0.f && u < 6.f) ? dgate / 6.f : 0.f;
+}
+
+// per channel, images in order: ds_p = ds / P, dbias = sum_b (g A + ds), dweight = sum_b (g X + ds_p S) -- the sums over the
+// BatchNorm output's gradient dx = g du + ds_p -- and the dx pass's coefficients coef = (dbias, dweight) / (B P) (eval: 0)
+__global__ void se_bwd_coef_kernel(const float* __restrict__ sums, const float* __restrict__ gate, const float* __restrict__ ds,
+                                   int B, int C, int P, int training, float* __restrict__ dweight, float* __restrict__ dbias,
+                                   float* __restrict__ coef, float* __restrict__ ds_p) {
+    const int c = blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= C) return;
+    const int rows = B * C;
+    float db = 0.f, dw = 0.f;
+    for (int b = 0; b < B; ++b) {
+        const int row = b * C + c;
+        const float g = gate[row], d = ds[row], dp = d / (float)P;
+        ds_p[row] = dp;
+        db += g * sums[row] + d;
+        dw += g * sums[rows + row] + dp * sums[2 * rows + row];
+    }
+    dbias[c] = db;
+    dweight[c] = dw;
+    const float n = (float)B * (float)P;
+    coef[c] = training ? db / n : 0.f;
+    coef[C + c] = training ? dw / n : 0.f;
+}
+
+__global__ __launch_bounds__(BA_T) void se_bwd_dx_kernel(const float* __restrict__ dy, const float* __restrict__ z,
+                                                         const float* __restrict__ mean, const float* __restrict__ invstd,
+                                                         const float* __restrict__ weight, const float* __restrict__ bias,
+                                                         const float* __restrict__ gate, const float* __restrict__ ds_p,
+                                                         const float* __restrict__ coef, int C, int P, int chunks, int act,
+                                                         float* __restrict__ dz) {
+    const int row = blockIdx.x / chunks, ch = blockIdx.x - row * chunks, c = row % C;
+    const float mu = mean[c], inv = invstd[c], gam = weight[c], bet = bias[c], gt = gate[row], dp = ds_p[row];
+    const float m1 = coef[c], m2 = coef[C + c], gi = gam * inv;
+    f32x4 vz[BA_V], vg[BA_V];
+    ba_load(z + (size_t)row * P, P, ch * BA_CHUNK, vz);
+    ba_load(dy + (size_t)row * P, P, ch * BA_CHUNK, vg);
+#pragma unroll
+    for (int i = 0; i < BA_V; ++i)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const float xh = (vz[i][e] - mu) * inv;
+            const float du = vg[i][e] * act_grad(fmaf(xh, gam, bet) * gt, act);
+            vg[i][e] = gi * (fmaf(gt, du, dp) - m1 - xh * m2);
+        }
+    ba_store(dz + (size_t)row * P, P, ch * BA_CHUNK, vg);
+}
+
 static int ba_chunks(int P) { return ceil_div(P, BA_CHUNK); }
+
+size_t se_act_bwd_workspace(int B, int C, int P) { return align_up((size_t)3 * B * C * ba_chunks(P) * sizeof(float), 256); }
+
+hipError_t se_act_bwd_reduce_run(const float* dy, const float* z, const float* mean, const float* invstd, const float* weight,
+                                 const float* bias, const float* gate, const float* a2, int B, int C, int P, int act, float* sums,
+                                 float* da2, void* ws, hipStream_t stream) {
+    const int chunks = ba_chunks(P), rows = B * C;
+    float* part = static_cast<float*>(ws);
+    hipLaunchKernelGGL(se_bwd_reduce_kernel, dim3(rows * chunks), dim3(BA_T), 0, stream, dy, z, mean, invstd, weight, bias, gate,
+                       rows, C, P, chunks, act, part);
+    hipLaunchKernelGGL(se_bwd_gate_kernel, dim3(ceil_div(rows, 256)), dim3(256), 0, stream, part, rows, C, chunks, weight, bias, a2,
+                       sums, da2);
+    return hipGetLastError();
+}
+
+hipError_t se_act_bwd_coef_run(const float* sums, const float* gate, const float* ds, int B, int C, int P, int training,
+                               float* dweight, float* dbias, float* coef, float* ds_p, hipStream_t stream) {
+    hipLaunchKernelGGL(se_bwd_coef_kernel, dim3(ceil_div(C, 256)), dim3(256), 0, stream, sums, gate, ds, B, C, P, training, dweight,
+                       dbias, coef, ds_p);
+    return hipGetLastError();
+}
+
+hipError_t se_act_bwd_dx_run(const float* dy, const float* z, const float* mean, const float* invstd, const float* weight,
+                             const float* bias, const float* gate, const float* ds_p, const float* coef, int B, int C, int P,
+                             int act, float* dz, hipStream_t stream) {
+    const int chunks = ba_chunks(P);
+    hipLaunchKernelGGL(se_bwd_dx_kernel, dim3(B * C * chunks), dim3(BA_T), 0, stream, dy, z, mean, invstd, weight, bias, gate,
+                       ds_p, coef, C, P, chunks, act, dz);
+    return hipGetLastError();
+}
 
 size_t bn_act_workspace(int B, int C, int P) {
     return align_up((size_t)2 * C * B * ba_chunks(P) * sizeof(float), 256) + align_up((size_t)2 * C * sizeof(float), 256);

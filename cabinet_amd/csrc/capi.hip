@@ -74,6 +74,15 @@ hipError_t bn_act_bwd_run(const float* dy, const float* x, const float* weight, 
 hipError_t bn_act_fwd_part_run(const float* x, const float* conv_part, int H, int W, const float* weight, const float* bias,
                                float* running_mean, float* running_var, const float* residual, int B, int C, int act, int training,
                                float momentum, float eps, float* y, float* save_mean, float* save_invstd, hipStream_t stream);
+size_t se_act_bwd_workspace(int B, int C, int P);
+hipError_t se_act_bwd_reduce_run(const float* dy, const float* z, const float* mean, const float* invstd, const float* weight,
+                                 const float* bias, const float* gate, const float* a2, int B, int C, int P, int act, float* sums,
+                                 float* da2, void* ws, hipStream_t stream);
+hipError_t se_act_bwd_coef_run(const float* sums, const float* gate, const float* ds, int B, int C, int P, int training,
+                               float* dweight, float* dbias, float* coef, float* ds_p, hipStream_t stream);
+hipError_t se_act_bwd_dx_run(const float* dy, const float* z, const float* mean, const float* invstd, const float* weight,
+                             const float* bias, const float* gate, const float* ds_p, const float* coef, int B, int C, int P,
+                             int act, float* dz, hipStream_t stream);
 size_t gate_act_workspace(int rows, int P);
 hipError_t gate_act_fwd_run(const float* x, const float* gate, int rows, int P, int act, float* y, hipStream_t stream);
 hipError_t gate_act_bwd_run(const float* dy, const float* x, const float* gate, int rows, int P, int act, float* dx,
@@ -910,6 +919,48 @@ int cabinet_gate_act_bwd(const float* dy, const float* x, const float* gate, int
     return hip_status(cabinet::gate_act_bwd_run(dy, x, gate, B * C, P, act, dx, dgate, workspace,
                                                 static_cast<hipStream_t>(stream)),
                       "gate_act_bwd launch");
+}
+
+// ------------------------------------------------------ squeeze-excite tail backward: act(SE(bn(z)))
+size_t cabinet_se_act_bwd_workspace_bytes(int B, int C, int P) {
+    return B > 0 && C > 0 && P > 0 ? cabinet::se_act_bwd_workspace(B, C, P) : 0;
+}
+
+int cabinet_se_act_bwd_reduce(const float* dy, const float* z, const float* mean, const float* invstd, const float* bn_weight,
+                              const float* bn_bias, const float* gate, const float* a2, int B, int C, int P, int act, float* sums,
+                              float* da2, void* workspace, size_t workspace_bytes, cabinet_stream_t stream) {
+    if (int rc = check_bn_act(B, C, P, act, "se_act_bwd_reduce")) return rc;
+    if (!dy || !z || !mean || !invstd || !bn_weight || !bn_bias || !gate || !a2 || !sums || !da2)
+        return fail(CABINET_ERR_INVALID_ARG, "se_act_bwd_reduce: null tensor pointer");
+    CABINET_REQUIRE_ALIGNED("se_act_bwd_reduce", dy, z);
+    const size_t need = cabinet::se_act_bwd_workspace(B, C, P);
+    if (!workspace || workspace_bytes < need)
+        return fail(CABINET_ERR_WORKSPACE, "se_act_bwd_reduce: workspace %zu < %zu bytes", workspace_bytes, need);
+    return hip_status(cabinet::se_act_bwd_reduce_run(dy, z, mean, invstd, bn_weight, bn_bias, gate, a2, B, C, P, act, sums, da2,
+                                                     workspace, static_cast<hipStream_t>(stream)),
+                      "se_act_bwd_reduce launch");
+}
+
+int cabinet_se_act_bwd_coef(const float* sums, const float* gate, const float* ds, int B, int C, int P, int training,
+                            float* dbn_weight, float* dbn_bias, float* coef, float* ds_over_p, cabinet_stream_t stream) {
+    if (B <= 0 || C <= 0 || P <= 0) return fail(CABINET_ERR_INVALID_ARG, "se_act_bwd_coef: non-positive dimension");
+    if (!sums || !gate || !ds || !dbn_weight || !dbn_bias || !coef || !ds_over_p)
+        return fail(CABINET_ERR_INVALID_ARG, "se_act_bwd_coef: null tensor pointer");
+    return hip_status(cabinet::se_act_bwd_coef_run(sums, gate, ds, B, C, P, training, dbn_weight, dbn_bias, coef, ds_over_p,
+                                                   static_cast<hipStream_t>(stream)),
+                      "se_act_bwd_coef launch");
+}
+
+int cabinet_se_act_bwd_dx(const float* dy, const float* z, const float* mean, const float* invstd, const float* bn_weight,
+                          const float* bn_bias, const float* gate, const float* ds_over_p, const float* coef, int B, int C, int P,
+                          int act, float* dz, cabinet_stream_t stream) {
+    if (int rc = check_bn_act(B, C, P, act, "se_act_bwd_dx")) return rc;
+    if (!dy || !z || !mean || !invstd || !bn_weight || !bn_bias || !gate || !ds_over_p || !coef || !dz)
+        return fail(CABINET_ERR_INVALID_ARG, "se_act_bwd_dx: null tensor pointer");
+    CABINET_REQUIRE_ALIGNED("se_act_bwd_dx", dy, z, dz);
+    return hip_status(cabinet::se_act_bwd_dx_run(dy, z, mean, invstd, bn_weight, bn_bias, gate, ds_over_p, coef, B, C, P, act, dz,
+                                                 static_cast<hipStream_t>(stream)),
+                      "se_act_bwd_dx launch");
 }
 
 // ------------------------------------------------------ BatchNorm (+act) -> depthwise convolution

@@ -5,6 +5,7 @@
 ``cab_local``       cab.py:182-184 and :213-216                           (K5)
 ``ffm_fused``       src/models/cabinet.py:142-153                         (K3 / K4; ``ffm_fused_upsampled`` + :228-230)
 ``bn_act``          cabinet.py:42-44 and every BatchNorm2d(+act) pair     (K7)     ``gate_act``  mobilenetv3.py:79-83
+``se_tail``         mobilenetv3.py:146-149 (BatchNorm -> SELayer -> act: K7 + gate_act forward, two-pass backward)
 ``bn_relu_cls``     cabinet.py:90-92, :161-172 (BN -> ReLU -> 1x1 classifier)  (K12)   ``conv3x3``  cabinet.py:59, :88-89, :160 (K11)
 ``dwconv`` / ``bn_act_dwconv``   mobilenetv3.py:118-126,135-143           (K8)
 ``stem_conv``       cabinet.py:111                                        (K9)     ``pwconv``   mobilenetv3.py:128-131
@@ -1237,6 +1238,96 @@ def gate_act(x, gate, act=None):
     if gate.shape != x.shape[:2]:
         raise RuntimeError(f"gate_act: gate {tuple(gate.shape)} does not match x {tuple(x.shape)}")
     return _GateAct.apply(x, gate, _ACT_CODES[act])
+
+
+# --------------------------------------------------------------------------- BatchNorm -> SELayer -> act (SE tail)
+
+
+class _SeTail(torch.autograd.Function):
+    """``act(se(bn(z)))`` with ``se(x) = x * hsig(fc2(relu(fc1(avgpool(x)))))`` as ONE autograd node.  The forward runs the
+    very kernels of the composed form (K7 BatchNorm, the stock pool, the MLP, gate_act_fwd: bitwise the same output); the
+    backward replaces gate_act_bwd + the pool's broadcast gradient + autograd's add + K7's reduce and dx by two passes over
+    (dy, z) (include/cabinet_hip.h: cabinet_se_act_bwd_*).  The MLP's backward is written out on (B, C) with autograd's
+    conventions at the clamp boundaries (ReLU: gradient where the output is > 0; ReLU6: where 0 < input < 6).  Saved for
+    backward: z, not the BatchNorm output."""
+
+    @staticmethod
+    @torch.amp.custom_fwd(device_type="cuda", cast_inputs=torch.float32)
+    def forward(fn_ctx, z, bn_w, bn_b, run_mean, run_var, w1, b1, w2, b2, act, training, momentum, eps):
+        lib = _lib.load()
+        z, bn_w, bn_b = _f32c(z), _f32c(bn_w), _f32c(bn_b)
+        B, C, H, W = z.shape
+        P = H * W
+        dev = z.device
+        x = torch.empty_like(z)
+        mean = torch.empty(C, dtype=torch.float32, device=dev)
+        invstd = torch.empty(C, dtype=torch.float32, device=dev)
+        ws, nbytes = _workspace(lib.cabinet_bn_act_workspace_bytes(B, C, P), dev)
+        with torch.cuda.device(dev):
+            rc = lib.cabinet_bn_act_fwd(_ptr(z), _ptr(bn_w), _ptr(bn_b), _ptr(run_mean), _ptr(run_var), None, B, C, P, 0,
+                                        int(training), float(momentum), float(eps), _ptr(x), _ptr(mean), _ptr(invstd), _ptr(ws),
+                                        nbytes, _stream_handle(dev))
+        _lib.check(rc, "cabinet_bn_act_fwd")
+        pooled = F.adaptive_avg_pool2d(x, 1).view(B, C)  # SELayer.gate (mobilenetv3.py:64-66), op for op
+        h1 = torch.relu(F.linear(pooled, w1, b1))
+        a2 = F.linear(h1, w2, b2)
+        gate = F.relu6(a2 + 3) / 6  # HardSigmoid (mobilenetv3.py:38-50)
+        y = torch.empty_like(z)
+        with torch.cuda.device(dev):
+            rc = lib.cabinet_gate_act_fwd(_ptr(x), _ptr(gate), B, C, P, act, _ptr(y), _stream_handle(dev))
+        _lib.check(rc, "cabinet_gate_act_fwd")
+        fn_ctx.save_for_backward(z, bn_w, bn_b, mean, invstd, pooled, h1, a2, gate, w1, w2)
+        fn_ctx.act, fn_ctx.training = act, bool(training)
+        return y
+
+    @staticmethod
+    @torch.amp.custom_bwd(device_type="cuda")
+    def backward(fn_ctx, g):
+        lib = _lib.load()
+        z, bn_w, bn_b, mean, invstd, pooled, h1, a2, gate, w1, w2 = fn_ctx.saved_tensors
+        g = _f32c(g)
+        B, C, H, W = z.shape
+        P = H * W
+        dev = z.device
+        stream = _stream_handle(dev)
+        sums = torch.empty((3, B, C), dtype=torch.float32, device=dev)  # sum_p du, sum_p du * xhat, sum_p xhat
+        da2 = torch.empty((B, C), dtype=torch.float32, device=dev)
+        ws, nbytes = _workspace(lib.cabinet_se_act_bwd_workspace_bytes(B, C, P), dev)
+        with torch.cuda.device(dev):
+            rc = lib.cabinet_se_act_bwd_reduce(_ptr(g), _ptr(z), _ptr(mean), _ptr(invstd), _ptr(bn_w), _ptr(bn_b), _ptr(gate), _ptr(a2),
+                                               B, C, P, fn_ctx.act, _ptr(sums), _ptr(da2), _ptr(ws), nbytes, stream)
+        _lib.check(rc, "cabinet_se_act_bwd_reduce")
+        dw2, db2 = da2.t().mm(h1), da2.sum(0)
+        da1 = da2.mm(w2) * (h1 > 0)
+        dw1, db1 = da1.t().mm(pooled), da1.sum(0)
+        ds = da1.mm(w1)  # gradient of the pooled input
+        dweight, dbias = torch.empty_like(bn_w), torch.empty_like(bn_b)
+        coef = torch.empty((2, C), dtype=torch.float32, device=dev)
+        ds_p = torch.empty((B, C), dtype=torch.float32, device=dev)
+        with torch.cuda.device(dev):
+            rc = lib.cabinet_se_act_bwd_coef(_ptr(sums), _ptr(gate), _ptr(ds), B, C, P, int(fn_ctx.training), _ptr(dweight),
+                                             _ptr(dbias), _ptr(coef), _ptr(ds_p), stream)
+        _lib.check(rc, "cabinet_se_act_bwd_coef")
+        dz = torch.empty_like(z)
+        with torch.cuda.device(dev):
+            rc = lib.cabinet_se_act_bwd_dx(_ptr(g), _ptr(z), _ptr(mean), _ptr(invstd), _ptr(bn_w), _ptr(bn_b), _ptr(gate), _ptr(ds_p),
+                                           _ptr(coef), B, C, P, fn_ctx.act, _ptr(dz), stream)
+        _lib.check(rc, "cabinet_se_act_bwd_dx")
+        return dz, dweight, dbias, None, None, dw1, db1, dw2, db2, None, None, None, None
+
+
+def se_tail(z, bn, se, act=None):
+    """``act(se(bn(z)))`` for a device tensor z (B,C,H,W): ``bn`` the nn.BatchNorm2d (running buffers updated in place in
+    training mode), ``se`` the SELayer (its ``fc.0`` / ``fc.2`` Linear layers), ``act`` None / "relu" / "hardswish" -- the
+    `BatchNorm, SELayer, act` run of the MBConv block (reference mobilenetv3.py:146-149, SELayer :68-83)."""
+    if not z.is_cuda:
+        raise RuntimeError("se_tail: device tensors only")
+    if act not in _ACT_CODES:
+        raise RuntimeError(f"se_tail: unknown activation {act!r}")
+    fc1, fc2 = se.fc[0], se.fc[2]
+    training, momentum = _bn_step(bn)
+    return _SeTail.apply(z, bn.weight, bn.bias, bn.running_mean, bn.running_var, fc1.weight, fc1.bias, fc2.weight, fc2.bias,
+                         _ACT_CODES[act], training, momentum, bn.eps)
 
 
 # --------------------------------------------------------------------------- BatchNorm (+act) -> depthwise conv, fused

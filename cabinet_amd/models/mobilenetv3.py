@@ -84,7 +84,7 @@ class _FusedSequential(nn.Sequential):
             y = super().forward(x)
             return y if residual is None else residual + y
         from ..functional import (bn_act, bn_act_dwconv, dwconv, dwconv_supported, gate_act, pwconv,
-                                  pwconv_supported)
+                                  pwconv_supported, se_tail)
 
         layers = [m for m in self if not isinstance(m, nn.Identity)]  # placeholders of the non-SE blocks: no-ops
 
@@ -95,7 +95,12 @@ class _FusedSequential(nn.Sequential):
         while i < len(layers):
             m = layers[i]
             nxt = layers[i + 1] if i + 1 < len(layers) else None
-            if isinstance(m, nn.BatchNorm2d):
+            if isinstance(m, nn.BatchNorm2d) and isinstance(nxt, SELayer):
+                # BatchNorm -> squeeze-excite -> activation as one operator (mobilenetv3.py:146-149): same forward kernels,
+                # a two-pass backward
+                act = act_of(layers[i + 2]) if i + 2 < len(layers) else None
+                x, i = se_tail(x, m, nxt, act), i + (3 if act else 2)
+            elif isinstance(m, nn.BatchNorm2d):
                 act = act_of(nxt)
                 nxt2 = layers[i + 2] if act and i + 2 < len(layers) else None
                 if isinstance(nxt2, nn.Conv2d) and nxt2.groups > 1 and dwconv_supported(nxt2):

@@ -416,6 +416,30 @@ int cabinet_gate_act_bwd(const float* dy, const float* x, const float* gate, int
                          float* dx, float* dgate, void* workspace, size_t workspace_bytes, cabinet_stream_t stream);
 
 /* ------------------------------------------------------------------------- *
+ * Backward of the squeeze-excite tail y = act(gate * x), x = bn(z), gate = hsig(W2 relu(W1 avgpool(x) + b1) + b2), of the
+ * MBConv blocks `dw -> BatchNorm -> SELayer -> act` (src/models/mobilenetv3.py:146-149, SELayer :68-83) in two passes over
+ * (dy, z) instead of the gate, pool, add and BatchNorm backward passes; the forward is cabinet_bn_act_fwd (act 0), the
+ * caller's pool and MLP on (B,C), and cabinet_gate_act_fwd.  z (B,C,H,W), P = H*W; mean / invstd as cabinet_bn_act_fwd
+ * saved them; gate (B,C).  Deterministic.
+ *   reduce : sums [3][B][C] = (sum_p du, sum_p du * xhat, sum_p xhat), xhat = (z - mean) * invstd,
+ *            du = dy * act'(gate * (bn_weight * xhat + bn_bias)); and da2 (B,C), the gradient at the hard sigmoid's input
+ *            a2 (B,C): (bn_weight * X + bn_bias * A) / 6 where 0 < a2 + 3 < 6, else 0.
+ *   coef   : from sums, gate and ds (B,C), the gradient of the pooled input (the caller's MLP backward of da2):
+ *            ds_over_p = ds / P, dbn_bias = sum_b (gate A + ds), dbn_weight = sum_b (gate X + ds_over_p S) and
+ *            coef [2][C] = (dbn_bias, dbn_weight) / (B*P) (zeros when training == 0).
+ *   dx     : dz = bn_weight * invstd * (gate * du + ds_over_p - coef[0][c] - xhat * coef[1][c]).
+ * ------------------------------------------------------------------------- */
+size_t cabinet_se_act_bwd_workspace_bytes(int B, int C, int P);
+int cabinet_se_act_bwd_reduce(const float* dy, const float* z, const float* mean, const float* invstd, const float* bn_weight,
+                              const float* bn_bias, const float* gate, const float* a2, int B, int C, int P, int act,
+                              float* sums, float* da2, void* workspace, size_t workspace_bytes, cabinet_stream_t stream);
+int cabinet_se_act_bwd_coef(const float* sums, const float* gate, const float* ds, int B, int C, int P, int training,
+                            float* dbn_weight, float* dbn_bias, float* coef, float* ds_over_p, cabinet_stream_t stream);
+int cabinet_se_act_bwd_dx(const float* dy, const float* z, const float* mean, const float* invstd, const float* bn_weight,
+                          const float* bn_bias, const float* gate, const float* ds_over_p, const float* coef,
+                          int B, int C, int P, int act, float* dz, cabinet_stream_t stream);
+
+/* ------------------------------------------------------------------------- *
  * BatchNorm2d (+activation) followed by a depthwise convolution, as one operator.
  * Replaces `nn.BatchNorm2d(hidden), act, depthwise nn.Conv2d` of the MBConv block, src/models/mobilenetv3.py:135-143:
  * the normalised, activated (B,C,H,W) tensor is neither written nor re-read -- the convolution normalises while it
