@@ -119,6 +119,11 @@ size_t stem_conv_wrw_workspace(int B, int H, int W);
 hipError_t stem_conv_fwd_run(const float* x, const float* w, int B, int H, int W, float* y, hipStream_t stream);
 hipError_t stem_conv_wrw_run(const float* dy, const float* x, int B, int H, int W, float* dw, void* ws,
                              hipStream_t stream);
+// pwconv_wide.hip
+bool pwconv_wide_supported(int Ci, int Co, int P);
+size_t pwconv_wide_wgrad_workspace(int B, int Ci, int Co, int P);
+hipError_t pwconv_wide_wgrad_run(const float* dy, const float* x, int B, int Ci, int Co, int P, float* dw, void* ws,
+                                 hipStream_t stream);
 // pwconv.hip
 bool pwconv_supported(int Ci, int Co, int P);
 size_t pwconv_bwd_workspace(int B, int Ci, int Co, int P);
@@ -1071,6 +1076,34 @@ int cabinet_pwconv_bwd(const float* dy, const float* x, const float* w, int B, i
         return fail(CABINET_ERR_WORKSPACE, "pwconv_bwd: workspace %zu < %zu bytes", workspace_bytes, need);
     return hip_status(cabinet::pwconv_bwd_run(dy, x, w, B, Ci, Co, P, dx, dw, workspace, static_cast<hipStream_t>(stream)),
                       "pwconv_bwd launch");
+}
+
+// ------------------------------------------------------ wide pointwise convolution: weight gradient
+int cabinet_pwconv_wide_supported(int Ci, int Co, int P) {
+    return Ci > 0 && Co > 0 && P > 0 && cabinet::pwconv_wide_supported(Ci, Co, P) ? 1 : 0;
+}
+
+size_t cabinet_pwconv_wide_wgrad_workspace_bytes(int B, int Ci, int Co, int P) {
+    if (B <= 0 || Ci <= 0 || Co <= 0 || P <= 0 || !cabinet::pwconv_wide_supported(Ci, Co, P)) return 0;
+    if ((long long)B * ((P + 63) / 64) > (1ll << 30)) return 0;
+    return cabinet::pwconv_wide_wgrad_workspace(B, Ci, Co, P);
+}
+
+int cabinet_pwconv_wide_wgrad(const float* dy, const float* x, int B, int Ci, int Co, int P, float* dw, void* workspace,
+                              size_t workspace_bytes, cabinet_stream_t stream) {
+    if (B <= 0 || Ci <= 0 || Co <= 0 || P <= 0)
+        return fail(CABINET_ERR_INVALID_ARG, "pwconv_wide_wgrad: non-positive dimension");
+    if ((long long)B * ((P + 63) / 64) > (1ll << 30))
+        return fail(CABINET_ERR_UNSUPPORTED, "pwconv_wide_wgrad: B=%d, P=%d: more than 2^30 pixel chunks", B, P);
+    if (!cabinet::pwconv_wide_supported(Ci, Co, P))
+        return fail(CABINET_ERR_UNSUPPORTED, "pwconv_wide_wgrad: Ci=%d, Co=%d, P=%d (multiples of 8, <= 4096, P <= 2^21, max(Ci, Co) * P <= 2^28)",
+                    Ci, Co, P);
+    if (!dy || !x || !dw) return fail(CABINET_ERR_INVALID_ARG, "pwconv_wide_wgrad: null tensor pointer");
+    const size_t need = cabinet::pwconv_wide_wgrad_workspace(B, Ci, Co, P);
+    if (!workspace || workspace_bytes < need)
+        return fail(CABINET_ERR_WORKSPACE, "pwconv_wide_wgrad: workspace %zu < %zu bytes", workspace_bytes, need);
+    return hip_status(cabinet::pwconv_wide_wgrad_run(dy, x, B, Ci, Co, P, dw, workspace, static_cast<hipStream_t>(stream)),
+                      "pwconv_wide_wgrad launch");
 }
 
 // ------------------------------------------------------ dense 3x3 convolution (Winograd F(2x2,3x3), fp32 MFMA)

@@ -1495,6 +1495,68 @@ def pwconv(x, conv):
     return _PwConv.apply(x, conv.weight)
 
 
+# --------------------------------------------------------------------------- wide pointwise convolution: weight gradient (K14)
+
+
+# CABINET_PWCONV_WIDE=0: the wide 1x1 convolutions go back to the stock operator entirely (MIOpen weight gradient with its
+# NCHW -> NHWC copies) -- same-box A/B timing only
+PWCONV_WIDE_ENABLED = _os.environ.get("CABINET_PWCONV_WIDE", "1") != "0"
+
+
+def pwconv_wide_supported(conv, x):
+    """True for the bias-free stride-1 1x1 convolutions whose WEIGHT GRADIENT K14 computes straight on NCHW (every such
+    layer K10 does not take: reference mobilenetv3.py:128-131,144-151,193, cabinet.py:114) -- in a forward that records a
+    graph for autograd only; fp32 device tensors outside autocast.  Forward and input gradient stay the stock operator's."""
+    if not (PWCONV_WIDE_ENABLED and isinstance(conv, torch.nn.Conv2d) and x.is_cuda and x.dim() == 4):
+        return False
+    if not (conv.kernel_size == (1, 1) and conv.stride == (1, 1) and conv.padding == (0, 0) and conv.groups == 1
+            and conv.bias is None and conv.dilation == (1, 1)):
+        return False
+    if not (torch.is_grad_enabled() and conv.weight.requires_grad) or torch.is_autocast_enabled():
+        return False
+    if x.dtype != torch.float32 or conv.weight.dtype != torch.float32 or x.shape[0] < 1 or x.shape[2] * x.shape[3] < 1:
+        return False
+    return bool(_lib.load().cabinet_pwconv_wide_supported(conv.in_channels, conv.out_channels, x.shape[2] * x.shape[3]))
+
+
+class _PwConvWide(torch.autograd.Function):
+    """y = conv2d(x, weight) with the stock forward and input gradient; dw by cabinet_pwconv_wide_wgrad."""
+
+    @staticmethod
+    def forward(fn_ctx, x, weight):
+        y = F.conv2d(x, weight)
+        fn_ctx.save_for_backward(x, weight)
+        return y
+
+    @staticmethod
+    def backward(fn_ctx, g):
+        x, w = fn_ctx.saved_tensors
+        dx = None
+        if fn_ctx.needs_input_grad[0]:
+            dx = torch.ops.aten.convolution_backward(g, x, w, None, [1, 1], [0, 0], [1, 1], False, [0, 0], 1,
+                                                     [True, False, False])[0]
+        dw = None
+        if fn_ctx.needs_input_grad[1]:
+            lib = _lib.load()
+            xc, gc = _f32c(x), _f32c(g)
+            Co, Ci = w.shape[0], w.shape[1]
+            B, P = xc.shape[0], xc.shape[2] * xc.shape[3]
+            dw = torch.empty((Co, Ci, 1, 1), dtype=torch.float32, device=x.device)
+            ws, nbytes = _workspace(lib.cabinet_pwconv_wide_wgrad_workspace_bytes(B, Ci, Co, P), x.device)
+            with torch.cuda.device(x.device):
+                rc = lib.cabinet_pwconv_wide_wgrad(_ptr(gc), _ptr(xc), B, Ci, Co, P, _ptr(dw), _ptr(ws), nbytes,
+                                                   _stream_handle(x.device))
+            _lib.check(rc, "cabinet_pwconv_wide_wgrad")
+        return dx, dw
+
+
+def pwconv_wide(x, conv):
+    """1x1 convolution of a device tensor with the weights of ``conv`` (see pwconv_wide_supported)."""
+    if not x.is_cuda:
+        raise RuntimeError("pwconv_wide: device tensors only")
+    return _PwConvWide.apply(x, conv.weight)
+
+
 # --------------------------------------------------------------------------- evaluation tail (K13; no autograd)
 
 

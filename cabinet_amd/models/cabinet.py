@@ -26,7 +26,8 @@ import torch.nn.functional as F
 
 from .. import functional as _functional
 from ..functional import (batched_bn_counters, bn_act, bn_relu_cls, conv1x1, conv1x1_bias_supported, conv3x3, conv3x3_bn_part,
-                          conv3x3_supported, ffm_fused, ffm_fused_upsampled, stem_conv, stem_conv_supported)
+                          conv3x3_supported, ffm_fused, ffm_fused_upsampled, pwconv_wide, pwconv_wide_supported, stem_conv,
+                          stem_conv_supported)
 from .cab import ContextAggregationBlock
 from .constants import MODEL_CONFIG, MOBILENETV3_CFGS
 from .mobilenetv3 import MobileNetV3
@@ -53,7 +54,10 @@ def _conv3x3_bn_relu(conv: nn.Conv2d, bn: nn.BatchNorm2d, x: torch.Tensor, x1: O
     if _functional.CONV3X3_ENABLED and _is_plain_3x3(conv) and conv3x3_supported(x.shape[1], c1, conv.out_channels, x.shape[2], x.shape[3]):
         part = conv3x3_bn_part(x, conv.out_channels) if bn.training else None
         return bn_act(conv3x3(x, conv.weight, x1, part), bn, "relu", conv_part=part)
-    return bn_act(conv(x if x1 is None else torch.cat([x, x1], dim=1)), bn, "relu")
+    xin = x if x1 is None else torch.cat([x, x1], dim=1)
+    if pwconv_wide_supported(conv, xin):  # the spatial branch's 1x1 conv_out in training: NCHW weight gradient (K14)
+        return bn_act(pwconv_wide(xin, conv), bn, "relu")
+    return bn_act(conv(xin), bn, "relu")
 
 
 def _conv3x3_bn_relu_cls(conv: nn.Conv2d, bn: nn.BatchNorm2d, cls: nn.Conv2d, x: torch.Tensor,

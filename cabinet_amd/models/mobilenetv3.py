@@ -84,7 +84,7 @@ class _FusedSequential(nn.Sequential):
             y = super().forward(x)
             return y if residual is None else residual + y
         from ..functional import (bn_act, bn_act_dwconv, dwconv, dwconv_supported, gate_act, pwconv,
-                                  pwconv_supported, se_tail)
+                                  pwconv_supported, pwconv_wide, pwconv_wide_supported, se_tail)
 
         layers = [m for m in self if not isinstance(m, nn.Identity)]  # placeholders of the non-SE blocks: no-ops
 
@@ -118,6 +118,8 @@ class _FusedSequential(nn.Sequential):
                 x, i = pwconv(x, m), i + 1  # thin 1x1 conv on a large plane: streaming MFMA kernel, no NHWC copies
             elif isinstance(m, nn.Conv2d) and m.groups > 1 and dwconv_supported(m):
                 x, i = dwconv(x, m), i + 1  # depthwise stencil kernel (MIOpen only has its naive solver here)
+            elif pwconv_wide_supported(m, x):
+                x, i = pwconv_wide(x, m), i + 1  # wide 1x1 conv, training: stock forward / dx, NCHW weight gradient (K14)
             else:
                 x, i = m(x), i + 1
         return x if residual is None else residual + x

@@ -486,6 +486,20 @@ int cabinet_pwconv_bwd(const float* dy, const float* x, const float* w, int B, i
                        float* dx, float* dw, void* workspace, size_t workspace_bytes, cabinet_stream_t stream);
 
 /* ------------------------------------------------------------------------- *
+ * Weight gradient of the WIDE pointwise (1x1, bias-free, stride 1) convolutions, the ones cabinet_pwconv_supported leaves
+ * to the stock operator (src/models/mobilenetv3.py:128-131,144-151,193, cabinet.py:114): NCHW in, no layout copy,
+ *   dw (Co,Ci) = sum_{b,p} dy (B,Co,P) (x) x (B,Ci,P)
+ * exact-fp32 MFMA with fp32 accumulation, split over (image, 64-pixel chunk), ordered slab sum: no atomics, bit-reproducible,
+ * capturable (the workspace comes from the caller).  The forward and the input gradient stay with the stock operator.
+ * Supported: Ci, Co multiples of 8, <= 4096, P <= 2^21, max(Ci, Co) * P <= 2^28 (cabinet_pwconv_wide_supported).
+ * workspace: cabinet_pwconv_wide_wgrad_workspace_bytes (one (Co,Ci) slab per split of the pixels; at most 512).
+ * ------------------------------------------------------------------------- */
+int cabinet_pwconv_wide_supported(int Ci, int Co, int P);
+size_t cabinet_pwconv_wide_wgrad_workspace_bytes(int B, int Ci, int Co, int P);
+int cabinet_pwconv_wide_wgrad(const float* dy, const float* x, int B, int Ci, int Co, int P, float* dw,
+                              void* workspace, size_t workspace_bytes, cabinet_stream_t stream);
+
+/* ------------------------------------------------------------------------- *
  * Dense 3x3 convolution, stride 1, padding 1, no bias (nn.Conv2d(Ci, Co, 3, padding=1, bias=False)) as Winograd
  * F(2x2,3x3) on the exact-fp32 MFMA; input transform, the 16 products and the output transform in ONE launch.
  * Replaces src/models/cabinet.py:59 (`conva[0]`), :68 + :88-89 (`b1(torch.cat([x, feat], dim=1))`: the two inputs are read
