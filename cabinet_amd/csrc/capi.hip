@@ -134,13 +134,13 @@ hipError_t pwconv_bwd_run(const float* dy, const float* x, const float* w, int B
 int ohem_blocks(int B, int H, int W);
 hipError_t ohem_up_fwd_run(int nh, const float* const* low, const long long* labels, int B, int C, int Hl, int Wl, int H, int W,
                            float thresh, int ignore_lb, float* const* loss_px, float* const* blk_sum, int* const* blk_cnt,
-                           hipStream_t stream);
+                           const float* const* class_weight, hipStream_t stream);
 hipError_t ohem_stats_run(const float* blk_sum, const int* blk_cnt, int nheads, int nblk, double* stats, hipStream_t stream);
 size_t ohem_up_bwd_workspace(int B, int C, int H, int Wl);
 bool ohem_up_supported(int C, int Wl, int W);
 hipError_t ohem_up_bwd_run(int nh, const float* const* low, const long long* labels, const float* const* loss_px, int B, int C,
                            int Hl, int Wl, int H, int W, float thresh, int ignore_lb, float coef, float* dlow, void* ws,
-                           hipStream_t stream);
+                           const float* const* class_weight, hipStream_t stream);
 // conv3x3_wino.hip
 struct WinoShape {
     int B, C0, C1, K, H, W;
@@ -436,16 +436,25 @@ int cabinet_ohem_up_blocks(int B, int H, int W) {
     return cabinet::ohem_blocks(B, H, W);
 }
 
-int cabinet_ohem_up_fwd(const float* logits_low, const long long* labels, int B, int C, int Hl, int Wl, int H, int W,
-                        float thresh, int ignore_lb, float* loss_px, float* blk_sum, int* blk_cnt,
-                        cabinet_stream_t stream) {
+// The class-weighted forms (`_w_`) carry the whole implementation; a null weight table selects the unweighted kernel
+// instantiations, which is all the original entry points below them do.
+int cabinet_ohem_up_w_fwd(const float* logits_low, const long long* labels, int B, int C, int Hl, int Wl, int H, int W,
+                          float thresh, int ignore_lb, float* loss_px, float* blk_sum, int* blk_cnt,
+                          const float* class_weight, cabinet_stream_t stream) {
     if (int rc = check_ohem(B, C, Hl, Wl, H, W)) return rc;
     if (!logits_low || !labels || !loss_px || !blk_sum || !blk_cnt)
         return fail(CABINET_ERR_INVALID_ARG, "ohem_up_fwd: null tensor pointer");
     CABINET_REQUIRE_ALIGNED("ohem_up_fwd", logits_low, labels, loss_px);
     return hip_status(cabinet::ohem_up_fwd_run(1, &logits_low, labels, B, C, Hl, Wl, H, W, thresh, ignore_lb, &loss_px, &blk_sum,
-                                               &blk_cnt, static_cast<hipStream_t>(stream)),
+                                               &blk_cnt, &class_weight, static_cast<hipStream_t>(stream)),
                       "ohem_up_fwd launch");
+}
+
+int cabinet_ohem_up_fwd(const float* logits_low, const long long* labels, int B, int C, int Hl, int Wl, int H, int W,
+                        float thresh, int ignore_lb, float* loss_px, float* blk_sum, int* blk_cnt,
+                        cabinet_stream_t stream) {
+    return cabinet_ohem_up_w_fwd(logits_low, labels, B, C, Hl, Wl, H, W, thresh, ignore_lb, loss_px, blk_sum, blk_cnt, nullptr,
+                                 stream);
 }
 
 int cabinet_ohem_stats(const float* blk_sum, const int* blk_cnt, int nheads, int nblk, double* stats, cabinet_stream_t stream) {
@@ -460,9 +469,9 @@ size_t cabinet_ohem_up_bwd_workspace_bytes(int B, int C, int Hl, int Wl, int H, 
     return cabinet::ohem_up_bwd_workspace(B, C, H, Wl);
 }
 
-int cabinet_ohem_up_bwd(const float* logits_low, const long long* labels, const float* loss_px, int B, int C, int Hl,
-                        int Wl, int H, int W, float thresh, int ignore_lb, float coef, float* dlogits_low,
-                        void* workspace, size_t workspace_bytes, cabinet_stream_t stream) {
+int cabinet_ohem_up_w_bwd(const float* logits_low, const long long* labels, const float* loss_px, int B, int C, int Hl,
+                          int Wl, int H, int W, float thresh, int ignore_lb, float coef, float* dlogits_low,
+                          void* workspace, size_t workspace_bytes, const float* class_weight, cabinet_stream_t stream) {
     if (int rc = check_ohem(B, C, Hl, Wl, H, W)) return rc;
     if (!logits_low || !labels || !loss_px || !dlogits_low)
         return fail(CABINET_ERR_INVALID_ARG, "ohem_up_bwd: null tensor pointer");
@@ -471,14 +480,22 @@ int cabinet_ohem_up_bwd(const float* logits_low, const long long* labels, const 
     if (!workspace || workspace_bytes < need)
         return fail(CABINET_ERR_WORKSPACE, "ohem_up_bwd: workspace %zu < %zu bytes", workspace_bytes, need);
     return hip_status(cabinet::ohem_up_bwd_run(1, &logits_low, labels, &loss_px, B, C, Hl, Wl, H, W, thresh, ignore_lb, coef,
-                                               dlogits_low, workspace, static_cast<hipStream_t>(stream)),
+                                               dlogits_low, workspace, &class_weight, static_cast<hipStream_t>(stream)),
                       "ohem_up_bwd launch");
 }
 
+int cabinet_ohem_up_bwd(const float* logits_low, const long long* labels, const float* loss_px, int B, int C, int Hl,
+                        int Wl, int H, int W, float thresh, int ignore_lb, float coef, float* dlogits_low,
+                        void* workspace, size_t workspace_bytes, cabinet_stream_t stream) {
+    return cabinet_ohem_up_w_bwd(logits_low, labels, loss_px, B, C, Hl, Wl, H, W, thresh, ignore_lb, coef, dlogits_low, workspace,
+                                 workspace_bytes, nullptr, stream);
+}
+
 // both loss heads of the step (same labels, same shapes) per launch
-int cabinet_ohem_up_pair_fwd(const float* logits_low_a, const float* logits_low_b, const long long* labels, int B, int C, int Hl,
-                             int Wl, int H, int W, float thresh, int ignore_lb, float* loss_px, float* blk_sum, int* blk_cnt,
-                             cabinet_stream_t stream) {
+int cabinet_ohem_up_pair_w_fwd(const float* logits_low_a, const float* logits_low_b, const long long* labels, int B, int C,
+                               int Hl, int Wl, int H, int W, float thresh, int ignore_lb, float* loss_px, float* blk_sum,
+                               int* blk_cnt, const float* class_weight_a, const float* class_weight_b,
+                               cabinet_stream_t stream) {
     if (int rc = check_ohem(B, C, Hl, Wl, H, W)) return rc;
     if (!logits_low_a || !logits_low_b || !labels || !loss_px || !blk_sum || !blk_cnt)
         return fail(CABINET_ERR_INVALID_ARG, "ohem_up_pair_fwd: null tensor pointer");
@@ -488,18 +505,27 @@ int cabinet_ohem_up_pair_fwd(const float* logits_low_a, const float* logits_low_
     float* lp[2] = {loss_px, loss_px + (size_t)B * H * W};
     float* bs[2] = {blk_sum, blk_sum + nblk};
     int* bc[2] = {blk_cnt, blk_cnt + 2 * nblk};
-    return hip_status(cabinet::ohem_up_fwd_run(2, low, labels, B, C, Hl, Wl, H, W, thresh, ignore_lb, lp, bs, bc,
+    const float* cw[2] = {class_weight_a, class_weight_b};
+    return hip_status(cabinet::ohem_up_fwd_run(2, low, labels, B, C, Hl, Wl, H, W, thresh, ignore_lb, lp, bs, bc, cw,
                                                static_cast<hipStream_t>(stream)),
                       "ohem_up_pair_fwd launch");
+}
+
+int cabinet_ohem_up_pair_fwd(const float* logits_low_a, const float* logits_low_b, const long long* labels, int B, int C, int Hl,
+                             int Wl, int H, int W, float thresh, int ignore_lb, float* loss_px, float* blk_sum, int* blk_cnt,
+                             cabinet_stream_t stream) {
+    return cabinet_ohem_up_pair_w_fwd(logits_low_a, logits_low_b, labels, B, C, Hl, Wl, H, W, thresh, ignore_lb, loss_px, blk_sum,
+                                      blk_cnt, nullptr, nullptr, stream);
 }
 
 size_t cabinet_ohem_up_pair_bwd_workspace_bytes(int B, int C, int Hl, int Wl, int H, int W) {
     return 2 * cabinet_ohem_up_bwd_workspace_bytes(B, C, Hl, Wl, H, W);
 }
 
-int cabinet_ohem_up_pair_bwd(const float* logits_low_a, const float* logits_low_b, const long long* labels, const float* loss_px,
-                             int B, int C, int Hl, int Wl, int H, int W, float thresh, int ignore_lb, float coef,
-                             float* dlogits_low, void* workspace, size_t workspace_bytes, cabinet_stream_t stream) {
+int cabinet_ohem_up_pair_w_bwd(const float* logits_low_a, const float* logits_low_b, const long long* labels,
+                               const float* loss_px, int B, int C, int Hl, int Wl, int H, int W, float thresh, int ignore_lb,
+                               float coef, float* dlogits_low, void* workspace, size_t workspace_bytes,
+                               const float* class_weight_a, const float* class_weight_b, cabinet_stream_t stream) {
     if (int rc = check_ohem(B, C, Hl, Wl, H, W)) return rc;
     if (!logits_low_a || !logits_low_b || !labels || !loss_px || !dlogits_low)
         return fail(CABINET_ERR_INVALID_ARG, "ohem_up_pair_bwd: null tensor pointer");
@@ -509,9 +535,17 @@ int cabinet_ohem_up_pair_bwd(const float* logits_low_a, const float* logits_low_
         return fail(CABINET_ERR_WORKSPACE, "ohem_up_pair_bwd: workspace %zu < %zu bytes", workspace_bytes, need);
     const float* low[2] = {logits_low_a, logits_low_b};
     const float* lp[2] = {loss_px, loss_px + (size_t)B * H * W};
+    const float* cw[2] = {class_weight_a, class_weight_b};
     return hip_status(cabinet::ohem_up_bwd_run(2, low, labels, lp, B, C, Hl, Wl, H, W, thresh, ignore_lb, coef, dlogits_low,
-                                               workspace, static_cast<hipStream_t>(stream)),
+                                               workspace, cw, static_cast<hipStream_t>(stream)),
                       "ohem_up_pair_bwd launch");
+}
+
+int cabinet_ohem_up_pair_bwd(const float* logits_low_a, const float* logits_low_b, const long long* labels, const float* loss_px,
+                             int B, int C, int Hl, int Wl, int H, int W, float thresh, int ignore_lb, float coef,
+                             float* dlogits_low, void* workspace, size_t workspace_bytes, cabinet_stream_t stream) {
+    return cabinet_ohem_up_pair_w_bwd(logits_low_a, logits_low_b, labels, loss_px, B, C, Hl, Wl, H, W, thresh, ignore_lb, coef,
+                                      dlogits_low, workspace, workspace_bytes, nullptr, nullptr, stream);
 }
 
 // ------------------------------------------------------ CAB local branch + block output

@@ -12,6 +12,19 @@
 //           T[b][c][oy][xs] = sum_ox wx(ox,xs) G[b][c][oy][ox]    (G recomputed on the fly, never stored)
 //           dlow[b][c][ys][xs] = sum_oy wy(oy,ys) T[b][c][oy][xs]
 //         no atomics -> bitwise reproducible (PyTorch's own upsample backward uses atomicAdd).
+//
+// Class weights (reference loss.py:38-80 with weight=w, what train.py:332-349 builds by default): every kernel that forms or
+// consumes the per-pixel loss has a second instantiation WT = true that takes a per-head table w of C floats (non-negative,
+// finite; a null table inside a weighted launch reads as all ones).  The per-pixel loss is l = w[label] (lse - x[label]):
+//   * loss_px keeps holding the UNWEIGHTED lse - x[label] (it is an internal buffer between the two passes), so the backward
+//     still rebuilds the forward's log-sum-exp bit for bit as loss_px + x[label], and w = 0 needs no division;
+//   * the selection is ohem_weighted(w[label], loss_px) > thresh -- the same fp32 product of the same two stored values in the
+//     forward and in every backward kernel, hence the same decision; #above and the sum are over that weighted loss, #valid
+//     does not look at the weights;
+//   * G = coef * sel * w[label] * (softmax - onehot): a per-pixel factor on coef (segment kernel, one-hot sums of the row / band
+//     kernels) or lse - log2 w[label] in the per-pixel shift of the row / band kernels' softmax part (w = 0: +inf, the pixel
+//     is switched off like an unselected one).  Nothing is added per (pixel, class).
+// WT = false is the code as it was: w = 1 is never multiplied in, and with -ffp-contract=off a table of ones gives its bits.
 #include <stdint.h>
 #include <stdlib.h>
 
@@ -19,6 +32,13 @@
 
 namespace cabinet {
 
+// per-head class-weight tables ((C,) fp32 device pointers; null = that head is unweighted)
+struct OhemWeights {
+    const float* w[2];
+};
+
+// the weighted per-pixel loss: ONE expression for the forward's statistics and for every backward kernel's selection
+__device__ __forceinline__ float ohem_weighted(float w, float loss) { return w * loss; }
 
 
 // One workgroup per output row (b, oy).  The two source rows are lerped vertically into LDS once (coalesced
@@ -26,12 +46,13 @@ namespace cabinet {
 // CMAX: classes rounded up, the per-class loops are fully unrolled.  EXACT (C == CMAX: 8 and 19 classes have their own
 // instances) drops the `c < C` predicates: with a run-time C the compiler turns every class into its own uniform branch
 // (LDS read -> wait -> arithmetic, one class at a time); without them the 2 C LDS reads of a pixel are in flight together.
-template <int CMAX, bool EXACT>
+template <int CMAX, bool EXACT, bool WT>
 __global__ __launch_bounds__(256) void ohem_up_fwd_kernel(const float* __restrict__ low, const long long* __restrict__ labels,
                                                            int C, int Hl, int Wl, int H, int W, float rh, float rw,
                                                            float thresh, int ignore_lb, float* __restrict__ loss_px,
-                                                           float* __restrict__ blk_sum, int* __restrict__ blk_cnt) {
-    extern __shared__ __attribute__((aligned(16))) float v[];  // [C][Wl]
+                                                           float* __restrict__ blk_sum, int* __restrict__ blk_cnt,
+                                                           const float* __restrict__ cw) {
+    extern __shared__ __attribute__((aligned(16))) float v[];  // [C][Wl] (+ [32] class weights when WT)
     __shared__ float s_f[4];
     __shared__ int s_i[3][4];
     const int b = blockIdx.y, oy = blockIdx.x, P = H * W;
@@ -44,6 +65,10 @@ __global__ __launch_bounds__(256) void ohem_up_fwd_kernel(const float* __restric
         const int c = i / Wl, xs = i - c * Wl;
         const float* p = low_b + (size_t)c * plane;
         v[i] = (1.f - ly) * p[y0 * Wl + xs] + ly * p[y1 * Wl + xs];
+    }
+    float* sw = v + C * Wl;
+    if constexpr (WT) {
+        if (threadIdx.x < 32) sw[threadIdx.x] = (cw && (int)threadIdx.x < C) ? cw[threadIdx.x] : 1.f;
     }
     __syncthreads();
     float my_sum = 0.f;
@@ -74,12 +99,14 @@ __global__ __launch_bounds__(256) void ohem_up_fwd_kernel(const float* __restric
             // arithmetic sentinel summed over a wide row could wrap)
             my_valid += 1;
             my_bad |= (lb < 0 || lb >= (long long)C) ? 1 : 0;
-            if (loss > thresh) {
+            float wloss = loss;
+            if constexpr (WT) wloss = ohem_weighted((lb >= 0 && lb < (long long)C) ? sw[(int)lb] : 1.f, loss);
+            if (wloss > thresh) {
                 my_above += 1;
-                my_sum += loss;
+                my_sum += wloss;
             }
         }
-        loss_px[pix] = loss;
+        loss_px[pix] = loss;  // unweighted, also when WT
     }
     // ordered block reduction
     my_sum = wave_sum(my_sum);
@@ -121,11 +148,11 @@ struct OhemFwdHeads {
     int* blk_cnt[NH];       // (nblk,2)
 };
 
-template <int CMAX, bool EXACT, int NH>
+template <int CMAX, bool EXACT, int NH, bool WT>
 __global__ __launch_bounds__(256) void ohem_up_fwd_x8_kernel(OhemFwdHeads<NH> hd, const long long* __restrict__ labels, int C,
                                                               int Hl, int Wl, int H, int W, float rh, float thresh,
-                                                              int ignore_lb) {
-    extern __shared__ __attribute__((aligned(16))) float v[];  // [NH][C][Wl]
+                                                              int ignore_lb, OhemWeights cw) {
+    extern __shared__ __attribute__((aligned(16))) float v[];  // [NH][C][Wl] (+ [NH][32] class weights when WT)
     __shared__ float s_f[NH][4];
     __shared__ int s_i[NH][3][4];
     // Grid (H, B) decoded XCD-aware (round 5): the dispatcher deals blocks round-robin over the 8 XCDs, so with
@@ -175,6 +202,13 @@ __global__ __launch_bounds__(256) void ohem_up_fwd_x8_kernel(OhemFwdHeads<NH> hd
                 const float* p = low_b + (size_t)c * plane;
                 v[hh * CW + i] = ((1.f - ly) * p[y0 * Wl + xs] + ly * p[y1 * Wl + xs]) * LOG2E_F;
             }
+        }
+    }
+    float* sw = v + NH * CW;
+    if constexpr (WT) {
+        for (int i = threadIdx.x; i < NH * 32; i += nt) {
+            const float* wp = cw.w[i >> 5];
+            sw[i] = (wp && (i & 31) < C) ? wp[i & 31] : 1.f;
         }
     }
     __syncthreads();
@@ -238,6 +272,7 @@ __global__ __launch_bounds__(256) void ohem_up_fwd_x8_kernel(OhemFwdHeads<NH> hd
             my_valid += valid ? 1 : 0;
             my_bad |= (valid && !inrange) ? 1 : 0;
             const int lrow = inrange ? (int)lb[j] * Wl : 0;
+            const int lcls = inrange ? (int)lb[j] : 0;
 #pragma unroll
             for (int hh = 0; hh < NH; ++hh) {
                 float loss = 0.f;
@@ -265,12 +300,14 @@ __global__ __launch_bounds__(256) void ohem_up_fwd_x8_kernel(OhemFwdHeads<NH> hd
                         lse = pm + fast_log2(s2);
                     }
                     loss = ((big[hh] - xl) + lse) * LN2_F;
-                    if (loss > thresh) {
+                    float wloss = loss;
+                    if constexpr (WT) wloss = ohem_weighted(sw[hh * 32 + lcls], loss);
+                    if (wloss > thresh) {
                         my_above[hh] += 1;
-                        my_sum[hh] += loss;
+                        my_sum[hh] += wloss;
                     }
                 }
-                out[hh][j] = loss;
+                out[hh][j] = loss;  // unweighted, also when WT
             }
         }
 #pragma unroll
@@ -339,11 +376,11 @@ struct OhemBwdHeads {
     float* T[2];
 };
 
-template <int CMAX, bool EXACT, int FR>
+template <int CMAX, bool EXACT, int FR, bool WT>
 __global__ __launch_bounds__(OBX_T) void ohem_up_bwd_x_kernel(OhemBwdHeads hd, const long long* __restrict__ labels, int NH, int B,
                                                              int C, int Hl, int Wl, int H, int W, float rh, float rw, float thresh,
                                                              int ignore_lb, float coef, int SX, int nox_max, int R_,
-                                                             int gplane) {
+                                                             int gplane, OhemWeights cw) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int R = FR ? FR : R_;
     const int nseg = (Wl + SX - 1) / SX, items = nseg * H * B, per_xcd = (items + 7) >> 3;
@@ -365,6 +402,7 @@ __global__ __launch_bounds__(OBX_T) void ohem_up_bwd_x_kernel(OhemBwdHeads hd, c
     // read the same phase at consecutive words (a plain [c][i] layout is a 16-way bank conflict there).
     float* G = v + C * (SX + 4);          // [C][R * gplane]
     const int gsize = R * gplane;
+    float* sw = G + C * gsize;            // [32] class weights of this head (WT only)
     const size_t plane = (size_t)Hl * Wl;
     const float* low_b = low + (size_t)b * C * plane;
     int y0, y1;
@@ -379,13 +417,17 @@ __global__ __launch_bounds__(OBX_T) void ohem_up_bwd_x_kernel(OhemBwdHeads hd, c
             v[c * (SX + 4) + q] = ((1.f - ly) * p[y0 * Wl + vx0 + q] + ly * p[y1 * Wl + vx0 + q]) * LOG2E_F;  // exp2 domain
         }
     }
+    if constexpr (WT) {
+        const float* wp = cw.w[head];
+        if (threadIdx.x < 32) sw[threadIdx.x] = (wp && (int)threadIdx.x < C) ? wp[threadIdx.x] : 1.f;
+    }
     __syncthreads();
     for (int i = threadIdx.x; i < nox; i += OBX_T) {
         const int ox = ox_lo + i;
         const int gi = FR ? (i & (FR - 1)) * gplane + i / (FR ? FR : 1) : (i % R) * gplane + i / R;
         const bool inimg = !FR || (ox >= 0 && ox < W);
         int x0 = 0, x1 = 0;
-        float lx = 0.f, loss = 0.f;
+        float lx = 0.f, loss = 0.f, cf = coef;  // cf: coef times the label's class weight
         bool sel = false;
         long long lb = 0;
         if (inimg) {
@@ -393,7 +435,13 @@ __global__ __launch_bounds__(OBX_T) void ohem_up_bwd_x_kernel(OhemBwdHeads hd, c
             const size_t pix = (size_t)b * P + (size_t)oy * W + ox;
             lb = labels[pix];
             loss = loss_px[pix];
-            sel = lb != (long long)ignore_lb && loss > thresh;
+            if constexpr (WT) {
+                const float wl = (lb >= 0 && lb < (long long)C) ? sw[(int)lb] : 1.f;
+                sel = lb != (long long)ignore_lb && ohem_weighted(wl, loss) > thresh;
+                cf = coef * wl;
+            } else {
+                sel = lb != (long long)ignore_lb && loss > thresh;
+            }
         }
         // taps outside the staged window belong to a pixel no column of this segment receives from
         const bool inwin = x0 >= vx0 && x1 < vx0 + nvx;
@@ -408,7 +456,7 @@ __global__ __launch_bounds__(OBX_T) void ohem_up_bwd_x_kernel(OhemBwdHeads hd, c
             for (int c = 0; c < CMAX; ++c)
                 if (EXACT || c < C) {
                     const float xcv = (1.f - lx) * v[c * (SX + 4) + x0 - vx0] + lx * v[c * (SX + 4) + x1 - vx0];
-                    G[c * gsize + gi] = coef * fast_exp2(xcv - lse2) - (c == (int)lb ? coef : 0.f);
+                    G[c * gsize + gi] = cf * fast_exp2(xcv - lse2) - (c == (int)lb ? cf : 0.f);
                 }
         } else {
 #pragma unroll
@@ -470,10 +518,13 @@ __global__ __launch_bounds__(OBX_T) void ohem_up_bwd_x_kernel(OhemBwdHeads hd, c
 //     LDS and then in 8 IPL registers of the class-phase lane for all classes; and the one-hot part of (softmax - onehot),
 //     which only touches the label's class: its three weighted sums go to oh{L,M,R}[label][g], owned by the interval's thread.
 // Per pixel and class this leaves fma + sub + v_exp_f32 + ~2 fma.
-template <int IPL>
+// WT: the head's class weights live in ONE register per lane (lane c holds w[c], C <= 32) and phase 1 fetches w[label] with a
+// wave shuffle -- no LDS beyond the unweighted kernel's (C = 30 at Wl = 128 fills all 64 KB).  Every wave that runs phase 1 runs
+// it with all 64 lanes (Wl is a multiple of 64), so the lanes the shuffle reads from are active.
+template <int IPL, bool WT>
 __global__ __launch_bounds__(256) void ohem_up_bwd_x8row_kernel(OhemBwdHeads hd, const long long* __restrict__ labels, int NH,
                                                                 int B, int C, int Hl, int H, float rh, float thresh,
-                                                                int ignore_lb, float coef) {
+                                                                int ignore_lb, float coef, OhemWeights cw) {
     constexpr int Wl = 64 * IPL, W = 8 * Wl;
     extern __shared__ __attribute__((aligned(16))) float smem[];
     float* v = smem;                 // [C][Wl]  vertically interpolated logits of this output row, exp2 domain
@@ -488,6 +539,11 @@ __global__ __launch_bounds__(256) void ohem_up_bwd_x8row_kernel(OhemBwdHeads hd,
     const float* __restrict__ low = hd.low[head];
     const float* __restrict__ loss_px = hd.loss_px[head];
     float* __restrict__ T = hd.T[head];
+    float wreg = 1.f;  // lane c: w[c]
+    if constexpr (WT) {
+        const float* wp = cw.w[head];
+        if (wp && (tid & 63) < C) wreg = wp[tid & 63];
+    }
     const size_t plane = (size_t)Hl * Wl;
     int y0, y1;
     float ly;
@@ -539,19 +595,23 @@ __global__ __launch_bounds__(256) void ohem_up_bwd_x8row_kernel(OhemBwdHeads hd,
         for (int j = 0; j < 8; ++j) {
             const float lam = j < 4 ? ((float)j + 4.5f) * 0.125f : ((float)j - 3.5f) * 0.125f;
             const float t = j < 4 ? -(1.f - lam) : lam;
-            const bool sel = lb[j] != (long long)ignore_lb && ls[j] > thresh;
             const bool inrange = lb[j] >= 0 && lb[j] < (long long)C;
+            float wl = 1.f;
+            if constexpr (WT) wl = __shfl(wreg, inrange ? (int)lb[j] : 0, 64);
+            const bool sel = lb[j] != (long long)ignore_lb && (WT ? ohem_weighted(wl, ls[j]) : ls[j]) > thresh;
             const int lrow = inrange ? (int)lb[j] * Wl : 0;
             const float* vl = v + lrow;
             const float xl = j < 4 ? fmaf(t, vl[g] - vl[gm], vl[g]) : fmaf(t, vl[gp] - vl[g], vl[g]);  // the forward's x_label
-            out[j] = sel ? fmaf(ls[j], LOG2E_F, xl) : INFINITY;
+            // WT: w exp2(x - lse) = exp2(x - (lse - log2 w)); v_log_f32(1) = 0 exactly, w = 0 gives +inf (pixel switched off)
+            out[j] = sel ? (WT ? fmaf(ls[j], LOG2E_F, xl) - fast_log2(wl) : fmaf(ls[j], LOG2E_F, xl)) : INFINITY;
             if (sel && inrange) {  // one-hot part: this thread owns column g of every class row (j ascending: a fixed order)
+                const float a = WT ? wl * (1.f - lam) : 1.f - lam, bq = WT ? wl * lam : lam;
                 if (j < 4) {
-                    ohL[lrow + g] += 1.f - lam;
-                    ohM[lrow + g] += lam;
+                    ohL[lrow + g] += a;
+                    ohM[lrow + g] += bq;
                 } else {
-                    ohM[lrow + g] += 1.f - lam;
-                    ohR[lrow + g] += lam;
+                    ohM[lrow + g] += a;
+                    ohR[lrow + g] += bq;
                 }
             }
         }
@@ -622,10 +682,10 @@ __global__ __launch_bounds__(256) void ohem_up_bwd_x8row_kernel(OhemBwdHeads hd,
 // Hl-1 (rows H-4..H-1, all weight on the last row) included: fixed order, no atomics.  The two source rows are loaded ONCE per band
 // (the row kernel fetched them once per output row) and re-lerped per row with the forward's own expression, so lse = loss +
 // x_label still reconstructs the forward's log-sum-exp bit for bit.  Phases 1 and 2 are the row kernel's, per row.
-template <int IPL>
+template <int IPL, bool WT>
 __global__ __launch_bounds__(256) void ohem_up_bwd_x8band_kernel(OhemBwdHeads hd, const long long* __restrict__ labels, int NH,
                                                                  int B, int C, int Hl, int H, float rh, float thresh,
-                                                                 int ignore_lb, float coef) {
+                                                                 int ignore_lb, float coef, OhemWeights cw) {
     constexpr int Wl = 64 * IPL, W = 8 * Wl, NCI = 8;   // NCI: classes per wave (C <= 32)
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int CW = C * Wl;
@@ -643,6 +703,11 @@ __global__ __launch_bounds__(256) void ohem_up_bwd_x8band_kernel(OhemBwdHeads hd
     const float* __restrict__ low = hd.low[head];
     const float* __restrict__ loss_px = hd.loss_px[head];
     float* __restrict__ P = hd.T[head];   // [2][B][C][Hl][Wl]
+    float wreg = 1.f;  // lane c: w[c] (see the row kernel)
+    if constexpr (WT) {
+        const float* wp = cw.w[head];
+        if (wp && (tid & 63) < C) wreg = wp[tid & 63];
+    }
     const size_t plane = (size_t)Hl * Wl, half = (size_t)B * C * plane;
     const int oy_lo = max(8 * k + 4, 0), oy_hi = min(8 * k + 12, H);
     int ya, yb;   // the two source rows every output row of the band interpolates (the taps of its first row)
@@ -706,19 +771,22 @@ __global__ __launch_bounds__(256) void ohem_up_bwd_x8band_kernel(OhemBwdHeads hd
             for (int j = 0; j < 8; ++j) {
                 const float lam = j < 4 ? ((float)j + 4.5f) * 0.125f : ((float)j - 3.5f) * 0.125f;
                 const float t = j < 4 ? -(1.f - lam) : lam;
-                const bool sel = lb[j] != (long long)ignore_lb && ls[j] > thresh;
                 const bool inrange = lb[j] >= 0 && lb[j] < (long long)C;
+                float wl = 1.f;
+                if constexpr (WT) wl = __shfl(wreg, inrange ? (int)lb[j] : 0, 64);
+                const bool sel = lb[j] != (long long)ignore_lb && (WT ? ohem_weighted(wl, ls[j]) : ls[j]) > thresh;
                 const int lrow = inrange ? (int)lb[j] * Wl : 0;
                 const float* vl = v + lrow;
                 const float xl = j < 4 ? fmaf(t, vl[g] - vl[gm], vl[g]) : fmaf(t, vl[gp] - vl[g], vl[g]);
-                out[j] = sel ? fmaf(ls[j], LOG2E_F, xl) : INFINITY;
+                out[j] = sel ? (WT ? fmaf(ls[j], LOG2E_F, xl) - fast_log2(wl) : fmaf(ls[j], LOG2E_F, xl)) : INFINITY;
                 if (sel && inrange) {
+                    const float a = WT ? wl * (1.f - lam) : 1.f - lam, bq = WT ? wl * lam : lam;
                     if (j < 4) {
-                        ohL[lrow + g] += 1.f - lam;
-                        ohM[lrow + g] += lam;
+                        ohL[lrow + g] += a;
+                        ohM[lrow + g] += bq;
                     } else {
-                        ohM[lrow + g] += 1.f - lam;
-                        ohR[lrow + g] += lam;
+                        ohM[lrow + g] += a;
+                        ohR[lrow + g] += bq;
                     }
                 }
             }
@@ -861,36 +929,50 @@ __global__ __launch_bounds__(256) void ohem_up_bwd_y8_kernel(const float* __rest
 
 int ohem_blocks(int B, int H, int W) { (void)W; return B * H; }  // one partial per output row
 
-// nh = 1 | 2 heads over the same labels; head i: low[i] -> loss_px[i], blk_sum[i], blk_cnt[i]
+// room for a head's class-weight table behind a kernel's dynamic LDS
+constexpr size_t OHEM_WT_LDS = 32 * sizeof(float);
+
+// nh = 1 | 2 heads over the same labels; head i: low[i] -> loss_px[i], blk_sum[i], blk_cnt[i]; cw: null, or nh class-weight tables
+// (each (C,) or null).  All null = the unweighted instantiations, untouched by the weighted ones.
 hipError_t ohem_up_fwd_run(int nh, const float* const* low, const long long* labels, int B, int C, int Hl, int Wl, int H, int W,
                            float thresh, int ignore_lb, float* const* loss_px, float* const* blk_sum, int* const* blk_cnt,
-                           hipStream_t stream) {
+                           const float* const* cw, hipStream_t stream) {
+    const OhemWeights wts{{cw ? cw[0] : nullptr, (cw && nh == 2) ? cw[1] : nullptr}};
+    const bool wt = wts.w[0] || wts.w[1];
+    const size_t wlds = wt ? OHEM_WT_LDS : 0;
     // the x8 form needs 16-byte aligned label / loss rows (W % 8 == 0 holds) and one thread per source column
     bool x8 = Wl > 0 && W == 8 * Wl && (reinterpret_cast<uintptr_t>(labels) & 15) == 0;
     for (int i = 0; i < nh; ++i) x8 = x8 && (reinterpret_cast<uintptr_t>(loss_px[i]) & 15) == 0;
     const int nt8 = Wl >= 256 ? 256 : ((Wl + 63) / 64) * 64;
     // both heads in one workgroup (shared label tile, two independent exp / log chains per thread) when their row buffers fit
-    const bool pair = nh == 2 && x8 && (size_t)2 * C * Wl * sizeof(float) <= 60 * 1024;
-#define OHEM_FWD(CM, EX)                                                                                                \
+    const bool pair = nh == 2 && x8 && (size_t)2 * C * Wl * sizeof(float) + 2 * wlds <= 60 * 1024;
+#define OHEM_FWD_(CM, EX, WTV)                                                                                          \
     do {                                                                                                                \
         if (pair) {                                                                                                     \
             OhemFwdHeads<2> hd{{low[0], low[1]}, {loss_px[0], loss_px[1]}, {blk_sum[0], blk_sum[1]}, {blk_cnt[0], blk_cnt[1]}}; \
-            hipLaunchKernelGGL((ohem_up_fwd_x8_kernel<CM, EX, 2>), dim3(H, B), dim3(nt8), (size_t)2 * C * Wl * sizeof(float), \
-                               stream, hd, labels, C, Hl, Wl, H, W, (float)Hl / (float)H, thresh, ignore_lb);           \
+            hipLaunchKernelGGL((ohem_up_fwd_x8_kernel<CM, EX, 2, WTV>), dim3(H, B), dim3(nt8),                          \
+                               (size_t)2 * C * Wl * sizeof(float) + 2 * wlds, stream, hd, labels, C, Hl, Wl, H, W,       \
+                               (float)Hl / (float)H, thresh, ignore_lb, wts);                                            \
         } else {                                                                                                        \
             for (int i = 0; i < nh; ++i) {                                                                              \
                 if (x8) {                                                                                               \
                     OhemFwdHeads<1> hd{{low[i]}, {loss_px[i]}, {blk_sum[i]}, {blk_cnt[i]}};                             \
-                    hipLaunchKernelGGL((ohem_up_fwd_x8_kernel<CM, EX, 1>), dim3(H, B), dim3(nt8),                       \
-                                       (size_t)C * Wl * sizeof(float), stream, hd, labels, C, Hl, Wl, H, W,              \
-                                       (float)Hl / (float)H, thresh, ignore_lb);                                         \
+                    hipLaunchKernelGGL((ohem_up_fwd_x8_kernel<CM, EX, 1, WTV>), dim3(H, B), dim3(nt8),                  \
+                                       (size_t)C * Wl * sizeof(float) + wlds, stream, hd, labels, C, Hl, Wl, H, W,       \
+                                       (float)Hl / (float)H, thresh, ignore_lb, OhemWeights{{wts.w[i], nullptr}});       \
                 } else {                                                                                                \
-                    hipLaunchKernelGGL((ohem_up_fwd_kernel<CM, EX>), dim3(H, B), dim3(256), (size_t)C * Wl * sizeof(float), \
-                                       stream, low[i], labels, C, Hl, Wl, H, W, (float)Hl / (float)H, (float)Wl / (float)W, \
-                                       thresh, ignore_lb, loss_px[i], blk_sum[i], blk_cnt[i]);                          \
+                    hipLaunchKernelGGL((ohem_up_fwd_kernel<CM, EX, WTV>), dim3(H, B), dim3(256),                        \
+                                       (size_t)C * Wl * sizeof(float) + wlds, stream, low[i], labels, C, Hl, Wl, H, W,   \
+                                       (float)Hl / (float)H, (float)Wl / (float)W, thresh, ignore_lb, loss_px[i],        \
+                                       blk_sum[i], blk_cnt[i], wts.w[i]);                                                \
                 }                                                                                                       \
             }                                                                                                           \
         }                                                                                                               \
+    } while (0)
+#define OHEM_FWD(CM, EX)                                                                                                \
+    do {                                                                                                                \
+        if (wt) OHEM_FWD_(CM, EX, true);                                                                                \
+        else OHEM_FWD_(CM, EX, false);                                                                                  \
     } while (0)
     if (C == 8) OHEM_FWD(8, true);
     else if (C == 19) OHEM_FWD(19, true);
@@ -899,6 +981,7 @@ hipError_t ohem_up_fwd_run(int nh, const float* const* low, const long long* lab
     else if (C <= 20) OHEM_FWD(20, false);
     else OHEM_FWD(32, false);
 #undef OHEM_FWD
+#undef OHEM_FWD_
     return hipGetLastError();
 }
 
@@ -939,10 +1022,13 @@ static bool os_row_kernel_enabled() {
     return !(e && e[0] == '1');
 }
 
-// nh heads: dlow is (nh, B, C, Hl, Wl) contiguous, the workspace holds nh T slabs
+// nh heads: dlow is (nh, B, C, Hl, Wl) contiguous, the workspace holds nh T slabs; cw as in ohem_up_fwd_run (the same tables
+// the forward that wrote loss_px was given: the selection is re-evaluated from them)
 hipError_t ohem_up_bwd_run(int nh, const float* const* low, const long long* labels, const float* const* loss_px, int B, int C,
                            int Hl, int Wl, int H, int W, float thresh, int ignore_lb, float coef, float* dlow, void* ws,
-                           hipStream_t stream) {
+                           const float* const* cw, hipStream_t stream) {
+    const OhemWeights wts{{cw ? cw[0] : nullptr, (cw && nh == 2) ? cw[1] : nullptr}};
+    const bool wt = wts.w[0] || wts.w[1];
     float* T = static_cast<float*>(ws);
     const size_t slab = ohem_up_bwd_workspace(B, C, H, Wl) / sizeof(float);
     OhemBwdHeads hd{};
@@ -970,49 +1056,67 @@ hipError_t ohem_up_bwd_run(int nh, const float* const* low, const long long* lab
     if ((ipl == 1 || ipl == 2 || ipl == 4) && aligned && lds_band <= 64 * 1024 && H == 8 * Hl && C <= 32 && os_row_kernel_enabled() &&
         band_enabled() && (reinterpret_cast<uintptr_t>(dlow) & 15) == 0) {
         const int bgrid = 8 * nh * ceil_div((Hl + 1) * B, 8);
-        static lds_attr_mask b1{0}, b2{0}, b4{0};
-#define OHEM_BAND(I, M)                                                                                                  \
+        static lds_attr_mask b1{0}, b2{0}, b4{0}, bw1{0}, bw2{0}, bw4{0};
+#define OHEM_BAND_(I, WTV, M)                                                                                            \
         do {                                                                                                             \
-            if (hipError_t e = ensure_dynamic_lds(reinterpret_cast<const void*>(ohem_up_bwd_x8band_kernel<I>), 64 * 1024, M); \
+            if (hipError_t e = ensure_dynamic_lds(reinterpret_cast<const void*>(ohem_up_bwd_x8band_kernel<I, WTV>), 64 * 1024, M); \
                 e != hipSuccess)                                                                                         \
                 return e;                                                                                                \
-            hipLaunchKernelGGL((ohem_up_bwd_x8band_kernel<I>), dim3(bgrid), dim3(256), lds_band, stream, hd, labels, nh, B, C, Hl, \
-                               H, (float)Hl / (float)H, thresh, ignore_lb, coef);                                        \
+            hipLaunchKernelGGL((ohem_up_bwd_x8band_kernel<I, WTV>), dim3(bgrid), dim3(256), lds_band, stream, hd, labels, nh, B, \
+                               C, Hl, H, (float)Hl / (float)H, thresh, ignore_lb, coef, wts);                            \
         } while (0)
-        if (ipl == 1) OHEM_BAND(1, b1);
-        else if (ipl == 2) OHEM_BAND(2, b2);
-        else OHEM_BAND(4, b4);
+#define OHEM_BAND(I, M, MW)                                                                                              \
+        do {                                                                                                             \
+            if (wt) OHEM_BAND_(I, true, MW);                                                                             \
+            else OHEM_BAND_(I, false, M);                                                                                \
+        } while (0)
+        if (ipl == 1) OHEM_BAND(1, b1, bw1);
+        else if (ipl == 2) OHEM_BAND(2, b2, bw2);
+        else OHEM_BAND(4, b4, bw4);
 #undef OHEM_BAND
+#undef OHEM_BAND_
         const size_t half4 = (size_t)B * C * Hl * Wl / 4;
         hipLaunchKernelGGL(ohem_up_bwd_comb_kernel, dim3((unsigned)((half4 * nh + 255) / 256)), dim3(256), 0, stream, hd, nh, half4, dlow);
         return hipGetLastError();
     }
     if ((ipl == 1 || ipl == 2 || ipl == 4) && aligned && lds_row <= 64 * 1024 && os_row_kernel_enabled()) {
         const int rgrid = 8 * nh * ceil_div(H * B, 8);
-        static lds_attr_mask m1{0}, m2{0}, m4{0};
-#define OHEM_ROW(I, M)                                                                                                   \
+        static lds_attr_mask m1{0}, m2{0}, m4{0}, mw1{0}, mw2{0}, mw4{0};
+#define OHEM_ROW_(I, WTV, M)                                                                                             \
         do {                                                                                                             \
-            if (hipError_t e = ensure_dynamic_lds(reinterpret_cast<const void*>(ohem_up_bwd_x8row_kernel<I>), 64 * 1024, M);  \
+            if (hipError_t e = ensure_dynamic_lds(reinterpret_cast<const void*>(ohem_up_bwd_x8row_kernel<I, WTV>), 64 * 1024, M); \
                 e != hipSuccess)                                                                                         \
                 return e;                                                                                                \
-            hipLaunchKernelGGL((ohem_up_bwd_x8row_kernel<I>), dim3(rgrid), dim3(256), lds_row, stream, hd, labels, nh, B, C, Hl, \
-                               H, (float)Hl / (float)H, thresh, ignore_lb, coef);                                        \
+            hipLaunchKernelGGL((ohem_up_bwd_x8row_kernel<I, WTV>), dim3(rgrid), dim3(256), lds_row, stream, hd, labels, nh, B, C, \
+                               Hl, H, (float)Hl / (float)H, thresh, ignore_lb, coef, wts);                               \
         } while (0)
-        if (ipl == 1) OHEM_ROW(1, m1);
-        else if (ipl == 2) OHEM_ROW(2, m2);
-        else OHEM_ROW(4, m4);
+#define OHEM_ROW(I, M, MW)                                                                                               \
+        do {                                                                                                             \
+            if (wt) OHEM_ROW_(I, true, MW);                                                                              \
+            else OHEM_ROW_(I, false, M);                                                                                 \
+        } while (0)
+        if (ipl == 1) OHEM_ROW(1, m1, mw1);
+        else if (ipl == 2) OHEM_ROW(2, m2, mw2);
+        else OHEM_ROW(4, m4, mw4);
 #undef OHEM_ROW
+#undef OHEM_ROW_
     } else {
-#define OHEM_BWD(CM, EX)                                                                                                 \
+        const size_t lds_x = lds + (wt ? OHEM_WT_LDS : 0);  // the segment's buffers stop at 60 KB
+#define OHEM_BWD_(CM, EX, WTV)                                                                                           \
     do {                                                                                                                 \
         if (x8)                                                                                                          \
-            hipLaunchKernelGGL((ohem_up_bwd_x_kernel<CM, EX, 8>), dim3(xgrid), dim3(OBX_T), lds, stream,                 \
+            hipLaunchKernelGGL((ohem_up_bwd_x_kernel<CM, EX, 8, WTV>), dim3(xgrid), dim3(OBX_T), lds_x, stream,          \
                                hd, labels, nh, B, C, Hl, Wl, H, W, (float)Hl / (float)H, (float)Wl / (float)W, thresh,   \
-                               ignore_lb, coef, SX, nox_max, R, gplane);                                                  \
+                               ignore_lb, coef, SX, nox_max, R, gplane, wts);                                             \
         else                                                                                                             \
-            hipLaunchKernelGGL((ohem_up_bwd_x_kernel<CM, EX, 0>), dim3(xgrid), dim3(OBX_T), lds, stream,                 \
+            hipLaunchKernelGGL((ohem_up_bwd_x_kernel<CM, EX, 0, WTV>), dim3(xgrid), dim3(OBX_T), lds_x, stream,          \
                                hd, labels, nh, B, C, Hl, Wl, H, W, (float)Hl / (float)H, (float)Wl / (float)W, thresh,   \
-                               ignore_lb, coef, SX, nox_max, R, gplane);                                                  \
+                               ignore_lb, coef, SX, nox_max, R, gplane, wts);                                             \
+    } while (0)
+#define OHEM_BWD(CM, EX)                                                                                                 \
+    do {                                                                                                                 \
+        if (wt) OHEM_BWD_(CM, EX, true);                                                                                 \
+        else OHEM_BWD_(CM, EX, false);                                                                                   \
     } while (0)
     if (C == 8) OHEM_BWD(8, true);
     else if (C == 19) OHEM_BWD(19, true);
@@ -1021,6 +1125,7 @@ hipError_t ohem_up_bwd_run(int nh, const float* const* low, const long long* lab
     else if (C <= 20) OHEM_BWD(20, false);
     else OHEM_BWD(32, false);
 #undef OHEM_BWD
+#undef OHEM_BWD_
     }
     // the T slabs are contiguous only when slab == B*C*H*Wl exactly; run the y pass per head otherwise
     const size_t plane_floats = (size_t)B * C * H * Wl;

@@ -478,11 +478,25 @@ def ffm_fused(fsp, fcp, conv_w, bn, w1, w2):
 # --------------------------------------------------------------------------- OHEM-CE fused with the final upsample
 
 
-def ohem_up_fwd_hip(logits_low, labels, size, thresh, ignore_lb):
+def _class_weight(weight, logits):
+    """A criterion's class-weight buffer as the C ABI wants it: dense fp32 (C,) on the logits' device, or None.  The buffer of
+    a criterion under ``.half()`` / AMP may be half precision; no such pointer reaches the library.  A buffer that already is
+    fp32, contiguous and on the device is passed as it is (its ADDRESS is what a captured graph replays)."""
+    if weight is None:
+        return None
+    if weight.dim() != 1 or weight.shape[0] != logits.shape[1]:
+        raise RuntimeError(f"OhemCELoss: weight of shape {tuple(weight.shape)} for {logits.shape[1]} classes")
+    return _f32c(weight.detach().to(logits.device))
+
+
+def ohem_up_fwd_hip(logits_low, labels, size, thresh, ignore_lb, weight=None):
     """Per-pixel CE of bilinear_upsample(logits_low -> size) vs labels, never materialising the upsample.
-    Returns loss_px (B,H,W) and the three reduced statistics as ONE device tensor [n_valid, n_above, sum_above]."""
+    Returns loss_px (B,H,W) and the three reduced statistics as ONE device tensor [n_valid, n_above, sum_above].
+    ``weight`` (C,): per-class weights; the statistics are then over w[label] * CE while loss_px stays the unweighted CE (it is
+    the buffer the backward rebuilds the log-sum-exp from; hand ohem_up_bwd_hip the same weights)."""
     lib = _lib.load()
     logits_low, labels = _f32c(logits_low), _aligned(labels)
+    weight = _class_weight(weight, logits_low)
     B, C, Hl, Wl = logits_low.shape
     H, W = size
     dev = logits_low.device
@@ -491,27 +505,29 @@ def ohem_up_fwd_hip(logits_low, labels, size, thresh, ignore_lb):
     blk_sum = torch.empty(nblk, dtype=torch.float32, device=dev)
     blk_cnt = torch.empty((nblk, 2), dtype=torch.int32, device=dev)
     with torch.cuda.device(dev):
-        rc = lib.cabinet_ohem_up_fwd(_ptr(logits_low), _ptr(labels), B, C, Hl, Wl, H, W, float(thresh), int(ignore_lb),
-                                     _ptr(loss_px), _ptr(blk_sum), _ptr(blk_cnt), _stream_handle(dev))
-        _lib.check(rc, "cabinet_ohem_up_fwd")
+        rc = lib.cabinet_ohem_up_w_fwd(_ptr(logits_low), _ptr(labels), B, C, Hl, Wl, H, W, float(thresh), int(ignore_lb),
+                                       _ptr(loss_px), _ptr(blk_sum), _ptr(blk_cnt), _ptr(weight), _stream_handle(dev))
+        _lib.check(rc, "cabinet_ohem_up_w_fwd")
         stats = torch.empty(3, dtype=torch.float64, device=dev)
         rc = lib.cabinet_ohem_stats(_ptr(blk_sum), _ptr(blk_cnt), 1, nblk, _ptr(stats), _stream_handle(dev))
     _lib.check(rc, "cabinet_ohem_stats")
     return loss_px, stats
 
 
-def ohem_up_bwd_hip(logits_low, labels, loss_px, size, thresh, ignore_lb, coef):
+def ohem_up_bwd_hip(logits_low, labels, loss_px, size, thresh, ignore_lb, coef, weight=None):
     lib = _lib.load()
     logits_low, labels, loss_px = _f32c(logits_low), _aligned(labels), _f32c(loss_px)
+    weight = _class_weight(weight, logits_low)
     B, C, Hl, Wl = logits_low.shape
     H, W = size
     dev = logits_low.device
     dlow = torch.empty_like(logits_low)
     ws, nbytes = _workspace(lib.cabinet_ohem_up_bwd_workspace_bytes(B, C, Hl, Wl, H, W), dev)
     with torch.cuda.device(dev):
-        rc = lib.cabinet_ohem_up_bwd(_ptr(logits_low), _ptr(labels), _ptr(loss_px), B, C, Hl, Wl, H, W, float(thresh),
-                                     int(ignore_lb), float(coef), _ptr(dlow), _ptr(ws), nbytes, _stream_handle(dev))
-    _lib.check(rc, "cabinet_ohem_up_bwd")
+        rc = lib.cabinet_ohem_up_w_bwd(_ptr(logits_low), _ptr(labels), _ptr(loss_px), B, C, Hl, Wl, H, W, float(thresh),
+                                       int(ignore_lb), float(coef), _ptr(dlow), _ptr(ws), nbytes, _ptr(weight),
+                                       _stream_handle(dev))
+    _lib.check(rc, "cabinet_ohem_up_w_bwd")
     return dlow
 
 
@@ -519,28 +535,32 @@ class _OhemUpSelected(torch.autograd.Function):
     """loss = sum_above / n_above for the 'at least n_min pixels above thresh' branch (reference loss.py:74-75);
     forward statistics were produced by ohem_up_fwd_hip, backward runs the two adjoint kernels.  ``n_above`` is a DEVICE
     scalar: nothing of the step's data-dependent state is baked into a kernel argument, so the op can be replayed from a
-    captured hipGraph (cabinet_amd.train.GraphedTrainStep); the host only reads it to pick the branch."""
+    captured hipGraph (cabinet_amd.train.GraphedTrainStep); the host only reads it to pick the branch.
+    ``weight``: the class weights the forward statistics were formed with (a buffer: no gradient), or None."""
 
     @staticmethod
-    def forward(fn_ctx, logits_low, labels, loss_px, sum_above, n_above, size, thresh, ignore_lb):
+    def forward(fn_ctx, logits_low, labels, loss_px, sum_above, n_above, size, thresh, ignore_lb, weight=None):
         fn_ctx.save_for_backward(logits_low, labels, loss_px, n_above)
         fn_ctx.meta = (size, thresh, ignore_lb)
+        fn_ctx.weight = weight  # not through save_for_backward: an in-place update of the buffer is no autograd error
         return (sum_above / n_above).to(torch.float32)
 
     @staticmethod
     def backward(fn_ctx, g):
         logits_low, labels, loss_px, n_above = fn_ctx.saved_tensors
         size, thresh, ignore_lb = fn_ctx.meta
-        # the kernels produce U^T[sel * (softmax - onehot)]; upstream gradient and 1/n_above are device scalars folded in after
-        dlow = ohem_up_bwd_hip(logits_low, labels, loss_px, size, thresh, ignore_lb, 1.0)
-        return dlow * (g / n_above).to(torch.float32), None, None, None, None, None, None, None
+        # the kernels produce U^T[sel * w * (softmax - onehot)]; upstream gradient and 1/n_above are device scalars folded in after
+        dlow = ohem_up_bwd_hip(logits_low, labels, loss_px, size, thresh, ignore_lb, 1.0, fn_ctx.weight)
+        return dlow * (g / n_above).to(torch.float32), None, None, None, None, None, None, None, None
 
 
-def ohem_up_pair_fwd_hip(low_a, low_b, labels, size, thresh, ignore_lb):
+def ohem_up_pair_fwd_hip(low_a, low_b, labels, size, thresh, ignore_lb, weight_a=None, weight_b=None):
     """Both loss heads over the same labels in ONE launch (reference train.py:435 on the outputs of cabinet.py:240-245).
-    Returns loss_px (2,B,H,W) and stats (2,3) = per head [n_valid, n_above, sum_above] as one device tensor."""
+    Returns loss_px (2,B,H,W) and stats (2,3) = per head [n_valid, n_above, sum_above] as one device tensor.
+    ``weight_a`` / ``weight_b``: each head's own class weights or None (see ohem_up_fwd_hip)."""
     lib = _lib.load()
     low_a, low_b, labels = _f32c(low_a), _f32c(low_b), _aligned(labels)
+    weight_a, weight_b = _class_weight(weight_a, low_a), _class_weight(weight_b, low_b)
     B, C, Hl, Wl = low_a.shape
     H, W = size
     dev = low_a.device
@@ -549,28 +569,30 @@ def ohem_up_pair_fwd_hip(low_a, low_b, labels, size, thresh, ignore_lb):
     blk_sum = torch.empty((2, nblk), dtype=torch.float32, device=dev)
     blk_cnt = torch.empty((2, nblk, 2), dtype=torch.int32, device=dev)
     with torch.cuda.device(dev):
-        rc = lib.cabinet_ohem_up_pair_fwd(_ptr(low_a), _ptr(low_b), _ptr(labels), B, C, Hl, Wl, H, W, float(thresh),
-                                          int(ignore_lb), _ptr(loss_px), _ptr(blk_sum), _ptr(blk_cnt), _stream_handle(dev))
-        _lib.check(rc, "cabinet_ohem_up_pair_fwd")
+        rc = lib.cabinet_ohem_up_pair_w_fwd(_ptr(low_a), _ptr(low_b), _ptr(labels), B, C, Hl, Wl, H, W, float(thresh),
+                                            int(ignore_lb), _ptr(loss_px), _ptr(blk_sum), _ptr(blk_cnt), _ptr(weight_a),
+                                            _ptr(weight_b), _stream_handle(dev))
+        _lib.check(rc, "cabinet_ohem_up_pair_w_fwd")
         stats = torch.empty((2, 3), dtype=torch.float64, device=dev)
         rc = lib.cabinet_ohem_stats(_ptr(blk_sum), _ptr(blk_cnt), 2, nblk, _ptr(stats), _stream_handle(dev))
     _lib.check(rc, "cabinet_ohem_stats")
     return loss_px, stats
 
 
-def ohem_up_pair_bwd_hip(low_a, low_b, labels, loss_px, size, thresh, ignore_lb, coef):
+def ohem_up_pair_bwd_hip(low_a, low_b, labels, loss_px, size, thresh, ignore_lb, coef, weight_a=None, weight_b=None):
     lib = _lib.load()
     low_a, low_b, labels, loss_px = _f32c(low_a), _f32c(low_b), _aligned(labels), _f32c(loss_px)
+    weight_a, weight_b = _class_weight(weight_a, low_a), _class_weight(weight_b, low_b)
     B, C, Hl, Wl = low_a.shape
     H, W = size
     dev = low_a.device
     dlow = torch.empty((2, B, C, Hl, Wl), dtype=torch.float32, device=dev)
     ws, nbytes = _workspace(lib.cabinet_ohem_up_pair_bwd_workspace_bytes(B, C, Hl, Wl, H, W), dev)
     with torch.cuda.device(dev):
-        rc = lib.cabinet_ohem_up_pair_bwd(_ptr(low_a), _ptr(low_b), _ptr(labels), _ptr(loss_px), B, C, Hl, Wl, H, W,
-                                          float(thresh), int(ignore_lb), float(coef), _ptr(dlow), _ptr(ws), nbytes,
-                                          _stream_handle(dev))
-    _lib.check(rc, "cabinet_ohem_up_pair_bwd")
+        rc = lib.cabinet_ohem_up_pair_w_bwd(_ptr(low_a), _ptr(low_b), _ptr(labels), _ptr(loss_px), B, C, Hl, Wl, H, W,
+                                            float(thresh), int(ignore_lb), float(coef), _ptr(dlow), _ptr(ws), nbytes,
+                                            _ptr(weight_a), _ptr(weight_b), _stream_handle(dev))
+    _lib.check(rc, "cabinet_ohem_up_pair_w_bwd")
     return dlow
 
 
@@ -579,19 +601,20 @@ class _OhemUpSelectedPair(torch.autograd.Function):
     (reference loss.py:74-75) with ONE backward launch pair for both (see _OhemUpSelected for the single head)."""
 
     @staticmethod
-    def forward(fn_ctx, low_a, low_b, labels, loss_px, stats, size, thresh, ignore_lb):
+    def forward(fn_ctx, low_a, low_b, labels, loss_px, stats, size, thresh, ignore_lb, weight_a=None, weight_b=None):
         fn_ctx.save_for_backward(low_a, low_b, labels, loss_px, stats)
         fn_ctx.meta = (size, thresh, ignore_lb)
+        fn_ctx.weights = (weight_a, weight_b)
         return (stats[0, 2] / stats[0, 1] + stats[1, 2] / stats[1, 1]).to(torch.float32)
 
     @staticmethod
     def backward(fn_ctx, g):
         low_a, low_b, labels, loss_px, stats = fn_ctx.saved_tensors
         size, thresh, ignore_lb = fn_ctx.meta
-        dlow = ohem_up_pair_bwd_hip(low_a, low_b, labels, loss_px, size, thresh, ignore_lb, 1.0)
+        dlow = ohem_up_pair_bwd_hip(low_a, low_b, labels, loss_px, size, thresh, ignore_lb, 1.0, *fn_ctx.weights)
         scale = (g / stats[:, 1]).to(torch.float32)  # upstream gradient and 1 / n_above per head: device scalars
         dlow = dlow * scale.view(2, 1, 1, 1, 1)
-        return dlow[0], dlow[1], None, None, None, None, None, None
+        return dlow[0], dlow[1], None, None, None, None, None, None, None, None
 
 
 # --------------------------------------------------------------------------- CAB local branch + block output (K5)

@@ -50,7 +50,9 @@ class OhemCELoss(nn.Module):
         of reference cabinet.py:240-245 with loss.py:38-80 -- with the upsample, the softmax and the selection fused
         into hand-written kernels on HIP tensors (``cabinet_ohem_up_fwd/bwd``): neither the (B,C,H,W) logits nor
         their log-softmax nor the per-pixel gradient are materialised.  The kernels implement the branch
-        "at least n_min pixels above thresh"; class weights or the top-n_min branch take the composite path."""
+        "at least n_min pixels above thresh", with or without class weights (non-negative, as the reference's ENet
+        weights are; the weight buffer is read by the kernels, it gets no gradient); the top-n_min branch, CPU tensors
+        and more than 32 classes take the composite path."""
         prep = self._fused_launch(logits_low, labels, size)
         return self._fused_finish(prep, None)
 
@@ -58,7 +60,7 @@ class OhemCELoss(nn.Module):
     # and pay ONE host read-back for the branch decisions (see ohem_upsampled_pair).
     def _fused_launch(self, logits_low, labels, size):
         size = tuple(size) if size is not None else tuple(labels.shape[-2:])
-        fused = logits_low.is_cuda and not isinstance(self.weight, torch.Tensor) and logits_low.shape[1] <= 32
+        fused = logits_low.is_cuda and logits_low.shape[1] <= 32
         if not fused:
             return (logits_low, labels, size, None, None, None)
         from .functional import _f32c, ohem_up_fwd_hip
@@ -72,8 +74,11 @@ class OhemCELoss(nn.Module):
                                f"match logits batch {logits_low.shape[0]} x size {size} on {logits_low.device}")
         low = _f32c(logits_low)
         lab = labels.contiguous()
-        loss_px, stats = ohem_up_fwd_hip(low.detach(), lab, size, self.thresh, self.ignore_lb)
+        loss_px, stats = ohem_up_fwd_hip(low.detach(), lab, size, self.thresh, self.ignore_lb, self._class_weight())
         return (logits_low, labels, size, low, lab, (loss_px, stats))
+
+    def _class_weight(self):
+        return self.weight if isinstance(self.weight, torch.Tensor) else None
 
     def _fused_finish(self, prep, host_stats):
         logits_low, labels, size, low, lab, fwd = prep
@@ -89,7 +94,8 @@ class OhemCELoss(nn.Module):
             if n_valid == 0:
                 return torch.zeros((), device=logits_low.device, requires_grad=True)
             if n_above >= min(self.n_min, n_valid):
-                return _OhemUpSelected.apply(low, lab, loss_px, stats[2], stats[1], size, self.thresh, self.ignore_lb)
+                return _OhemUpSelected.apply(low, lab, loss_px, stats[2], stats[1], size, self.thresh, self.ignore_lb,
+                                             self._class_weight())
         up = F.interpolate(logits_low, size=size, mode="bilinear", align_corners=False)
         return self.forward(up, labels)
 
@@ -134,11 +140,11 @@ class _PairPrep:
 
 def fused_pair_launch(crit_a, low_a, crit_b, low_b, labels, size):
     """Forward kernels of both loss heads (reference train.py:435), ONE launch when the heads agree in shape, threshold and
-    ignore label (they do in the reference's step: two OhemCELoss(0.7, n_min, 255) on two (B,ncls,H/8,W/8) outputs), else one
-    launch per head.  No host synchronisation: ``prep.stats`` is a device tensor."""
+    ignore label (they do in the reference's step: two OhemCELoss(0.7, n_min, 255, weight) on two (B,ncls,H/8,W/8) outputs),
+    else one launch per head.  Each head brings its own class weights or none: the two criteria own separate buffers, and the
+    kernels take one table per head.  No host synchronisation: ``prep.stats`` is a device tensor."""
     size = tuple(size) if size is not None else tuple(labels.shape[-2:])
     same = (low_a.is_cuda and low_b.is_cuda and low_a.shape == low_b.shape and low_a.shape[1] <= 32
-            and not isinstance(crit_a.weight, torch.Tensor) and not isinstance(crit_b.weight, torch.Tensor)
             and (crit_a.thresh, crit_a.ignore_lb) == (crit_b.thresh, crit_b.ignore_lb))
     if not same:
         return _PairPrep((crit_a, crit_b), (low_a, low_b), labels, size,
@@ -151,7 +157,8 @@ def fused_pair_launch(crit_a, low_a, crit_b, low_b, labels, size):
         raise RuntimeError(f"OhemCELoss.forward_upsampled: labels {tuple(labels.shape)} on {labels.device} do not "
                            f"match logits batch {low_a.shape[0]} x size {size} on {low_a.device}")
     la, lb_, lab = _f32c(low_a), _f32c(low_b), labels.contiguous()
-    loss_px, stats = ohem_up_pair_fwd_hip(la.detach(), lb_.detach(), lab, size, crit_a.thresh, crit_a.ignore_lb)
+    loss_px, stats = ohem_up_pair_fwd_hip(la.detach(), lb_.detach(), lab, size, crit_a.thresh, crit_a.ignore_lb,
+                                          crit_a._class_weight(), crit_b._class_weight())
     return _PairPrep((crit_a, crit_b), (low_a, low_b), labels, size, pair=(la, lb_, lab, loss_px, stats))
 
 
@@ -174,7 +181,8 @@ def fused_pair_finish(prep, host_stats=None):
     if all(selected):
         from .functional import _OhemUpSelectedPair
 
-        return _OhemUpSelectedPair.apply(la, lb_, lab, loss_px, stats, prep.size, crit_a.thresh, crit_a.ignore_lb)
+        return _OhemUpSelectedPair.apply(la, lb_, lab, loss_px, stats, prep.size, crit_a.thresh, crit_a.ignore_lb,
+                                         crit_a._class_weight(), crit_b._class_weight())
     # a head on the rare top-n_min branch (or without a valid pixel): per-head paths (composite where needed)
     from .functional import _OhemUpSelected
 
@@ -185,7 +193,7 @@ def fused_pair_finish(prep, host_stats=None):
             term = torch.zeros((), device=low.device, requires_grad=True)
         elif ok:
             term = _OhemUpSelected.apply((la, lb_)[i], lab, loss_px[i], stats[i, 2], stats[i, 1], prep.size, crit.thresh,
-                                         crit.ignore_lb)
+                                         crit.ignore_lb, crit._class_weight())
         else:
             term = crit.forward(F.interpolate(low, size=prep.size, mode="bilinear", align_corners=False), prep.labels)
         total = term if total is None else total + term

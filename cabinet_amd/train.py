@@ -47,8 +47,14 @@ def build_model(mode="large", n_classes=8, device="cpu", seed=0, gamma=None, fre
     return net.to(device)
 
 
-def make_criteria(batch, height, width, device, thresh=DEFAULT_SCORE_THRESHOLD, ignore=DEFAULT_IGNORE_LABEL):
+def make_criteria(batch, height, width, device, thresh=DEFAULT_SCORE_THRESHOLD, ignore=DEFAULT_IGNORE_LABEL, weight=None):
+    """The step's two criteria.  ``weight``: per-class weights (a tensor or a sequence of ``n_classes`` floats), handed to both
+    criteria as the reference does (train.py:344-349); each criterion registers its own fp32 copy as a buffer."""
     n_min = max(1, batch * height * width // OHEM_DIVISOR)
+    if weight is not None:
+        weight = torch.as_tensor(weight, dtype=torch.float32).detach()
+        return (OhemCELoss(thresh, n_min, ignore, weight=weight.clone()).to(device),
+                OhemCELoss(thresh, n_min, ignore, weight=weight.clone()).to(device))
     return (OhemCELoss(thresh, n_min, ignore).to(device), OhemCELoss(thresh, n_min, ignore).to(device))
 
 
@@ -224,6 +230,9 @@ class GraphedTrainStep:
     scalar in the loss).  If the host read says a head needs the rare top-n_min branch (or has no valid pixel), the step
     restores the BatchNorm buffers graph A advanced and runs eagerly instead -- same result as TrainStep, just slower.
     Inputs are copied into static tensors; the returned loss is a static device tensor (read it before the next step).
+    Class weights (``criteria`` built with ``weight=``) are static tensors too: the graphs hold the ADDRESSES of the criteria's
+    weight buffers, so an in-place update (``crit.weight.copy_(w)``) is seen by the next replay, while rebinding
+    ``crit.weight = w`` (or ``.to()`` / ``.half()`` on the criterion) after capture is not -- build a new step for that.
     Data-parallel runs keep the eager TrainStep: its reducer launches collectives from autograd hooks."""
 
     def __init__(self, net, criteria, optimizer=None, warmup=2, capture_optimizer=False, before_optimizer=None):
@@ -252,7 +261,7 @@ class GraphedTrainStep:
             self.prep = fused_pair_launch(self.crit_p, low, self.crit_16, low16, self.s_lb, size)
             self.s_stats = self.prep.stats
             if self.s_stats is None:
-                raise RuntimeError("GraphedTrainStep needs the fused OHEM head (device logits, <= 32 classes, no class weights)")
+                raise RuntimeError("GraphedTrainStep needs the fused OHEM head (device logits, <= 32 classes)")
         # capture does not execute: replay once to learn the capture batch's branch, then undo its BatchNorm side effects
         self.snap.save()
         self.g_fwd.replay()
@@ -382,6 +391,7 @@ class GraphedDDPStep:
     ``torch._foreach_copy_`` per segment packs them into the flat fp32 buckets, and ``.grad`` then IS the bucket view the
     all-reduce averages and the optimizer reads.  (Pre-zeroed bucket views as ``.grad`` made autograd run one in-place add
     per parameter: ~180 extra launches per step.)  BatchNorm statistics and OHEM stay per rank.
+    Class weights of the criteria are static tensors of the graphs, exactly as in GraphedTrainStep: update them in place.
     ``use_graphs=False`` (default on CPU tensors) runs the identical schedule eagerly -- that is what the gloo tests drive."""
 
     DECODER = ("conv_out", "ffm", "ab")

@@ -221,6 +221,32 @@ size_t cabinet_ohem_up_pair_bwd_workspace_bytes(int B, int C, int Hl, int Wl, in
 int cabinet_ohem_up_pair_bwd(const float* logits_low_a, const float* logits_low_b, const long long* labels,
                              const float* loss_px, int B, int C, int Hl, int Wl, int H, int W, float thresh, int ignore_lb,
                              float coef, float* dlogits_low, void* workspace, size_t workspace_bytes, cabinet_stream_t stream);
+/* The same four with per-class weights -- reference loss.py:38-80 with `weight=w`, what src/scripts/train.py:332-349 builds
+ * from configs/train.yaml `cls_pw` by default.  class_weight[_a|_b]: (C,) fp32 on the device, non-negative and finite, one
+ * table per head (the two criteria own separate buffers); NULL = that head is unweighted, and with every table NULL these
+ * ARE the entry points above, bit for bit.  Argument lists = the unweighted ones plus the tables in front of the stream;
+ * workspaces are those of cabinet_ohem_up[_pair]_bwd_workspace_bytes.  (Added under ABI v8.)
+ *   per-pixel loss  l = w[label] * (lse - x[label])          (F.cross_entropy(weight=w, reduction="none"))
+ *   #valid          does not depend on w (a class of weight 0 is still valid)
+ *   selection       valid & (l > thresh); #above and the sum are over l; the caller forms sum / #above (a plain mean)
+ *   bwd             dlogits_low = coef * U^T[ sel * w[label] * (softmax - onehot) ]; no gradient w.r.t. the weights
+ * loss_px between the two passes holds the UNWEIGHTED lse - x[label] (the backward rebuilds lse from it and re-evaluates the
+ * selection as w[label] * loss_px > thresh with the forward's own product): hand the backward the forward's tables.        */
+int cabinet_ohem_up_w_fwd(const float* logits_low, const long long* labels,
+                          int B, int C, int Hl, int Wl, int H, int W, float thresh, int ignore_lb,
+                          float* loss_px, float* blk_sum, int* blk_cnt, const float* class_weight, cabinet_stream_t stream);
+int cabinet_ohem_up_w_bwd(const float* logits_low, const long long* labels, const float* loss_px,
+                          int B, int C, int Hl, int Wl, int H, int W, float thresh, int ignore_lb, float coef,
+                          float* dlogits_low, void* workspace, size_t workspace_bytes, const float* class_weight,
+                          cabinet_stream_t stream);
+int cabinet_ohem_up_pair_w_fwd(const float* logits_low_a, const float* logits_low_b, const long long* labels,
+                               int B, int C, int Hl, int Wl, int H, int W, float thresh, int ignore_lb,
+                               float* loss_px, float* blk_sum, int* blk_cnt,
+                               const float* class_weight_a, const float* class_weight_b, cabinet_stream_t stream);
+int cabinet_ohem_up_pair_w_bwd(const float* logits_low_a, const float* logits_low_b, const long long* labels,
+                               const float* loss_px, int B, int C, int Hl, int Wl, int H, int W, float thresh, int ignore_lb,
+                               float coef, float* dlogits_low, void* workspace, size_t workspace_bytes,
+                               const float* class_weight_a, const float* class_weight_b, cabinet_stream_t stream);
 
 /* ------------------------------------------------------------------------- *
  * CAB local branch + block output.
