@@ -140,7 +140,11 @@ size_t ohem_up_bwd_workspace(int B, int C, int H, int Wl);
 bool ohem_up_supported(int C, int Wl, int W);
 hipError_t ohem_up_bwd_run(int nh, const float* const* low, const long long* labels, const float* const* loss_px, int B, int C,
                            int Hl, int Wl, int H, int W, float thresh, int ignore_lb, float coef, float* dlow, void* ws,
-                           const float* const* class_weight, hipStream_t stream);
+                           const float* const* cw, const double* dsel, hipStream_t stream);
+size_t ohem_select_workspace(int nheads);
+hipError_t ohem_select_run(int nheads, const float* const* loss_px, const long long* labels, const double* stats, long long P, int C,
+                           float thresh, const int* n_min, int ignore_lb, const float* const* cw, double* sel, void* ws,
+                           hipStream_t stream);
 // conv3x3_wino.hip
 struct WinoShape {
     int B, C0, C1, K, H, W;
@@ -480,7 +484,7 @@ int cabinet_ohem_up_w_bwd(const float* logits_low, const long long* labels, cons
     if (!workspace || workspace_bytes < need)
         return fail(CABINET_ERR_WORKSPACE, "ohem_up_bwd: workspace %zu < %zu bytes", workspace_bytes, need);
     return hip_status(cabinet::ohem_up_bwd_run(1, &logits_low, labels, &loss_px, B, C, Hl, Wl, H, W, thresh, ignore_lb, coef,
-                                               dlogits_low, workspace, &class_weight, static_cast<hipStream_t>(stream)),
+                                               dlogits_low, workspace, &class_weight, nullptr, static_cast<hipStream_t>(stream)),
                       "ohem_up_bwd launch");
 }
 
@@ -537,7 +541,7 @@ int cabinet_ohem_up_pair_w_bwd(const float* logits_low_a, const float* logits_lo
     const float* lp[2] = {loss_px, loss_px + (size_t)B * H * W};
     const float* cw[2] = {class_weight_a, class_weight_b};
     return hip_status(cabinet::ohem_up_bwd_run(2, low, labels, lp, B, C, Hl, Wl, H, W, thresh, ignore_lb, coef, dlogits_low,
-                                               workspace, cw, static_cast<hipStream_t>(stream)),
+                                               workspace, cw, nullptr, static_cast<hipStream_t>(stream)),
                       "ohem_up_pair_bwd launch");
 }
 
@@ -546,6 +550,69 @@ int cabinet_ohem_up_pair_bwd(const float* logits_low_a, const float* logits_low_
                              float* dlogits_low, void* workspace, size_t workspace_bytes, cabinet_stream_t stream) {
     return cabinet_ohem_up_pair_w_bwd(logits_low_a, logits_low_b, labels, loss_px, B, C, Hl, Wl, H, W, thresh, ignore_lb, coef,
                                       dlogits_low, workspace, workspace_bytes, nullptr, nullptr, stream);
+}
+
+// The top-n_min branch on the device: selection into sel (nheads,4), then the backward kernels read [t, tie] from it.
+size_t cabinet_ohem_select_workspace_bytes(int nheads, int B, int H, int W) {
+    if (nheads < 1 || nheads > 2 || B <= 0 || H <= 0 || W <= 0) return 0;
+    return cabinet::ohem_select_workspace(nheads);
+}
+
+int cabinet_ohem_select(const float* loss_px, const long long* labels, const double* stats, int nheads, int B, int C, int H, int W,
+                        float thresh, int n_min_a, int n_min_b, int ignore_lb, const float* class_weight_a,
+                        const float* class_weight_b, double* sel, void* workspace, size_t workspace_bytes,
+                        cabinet_stream_t stream) {
+    if (nheads < 1 || nheads > 2) return fail(CABINET_ERR_INVALID_ARG, "ohem_select: nheads=%d (1 or 2)", nheads);
+    if (B <= 0 || C <= 0 || H <= 0 || W <= 0) return fail(CABINET_ERR_INVALID_ARG, "ohem_select: non-positive dimension");
+    if (C > 32) return fail(CABINET_ERR_UNSUPPORTED, "ohem_select: C=%d classes (max 32)", C);
+    if ((long long)B * H * W >= (1ll << 31)) return fail(CABINET_ERR_UNSUPPORTED, "ohem_select: B*H*W exceeds 2^31 - 1 pixels");
+    if (n_min_a < 0 || n_min_b < 0) return fail(CABINET_ERR_INVALID_ARG, "ohem_select: negative n_min");
+    if (!loss_px || !labels || !stats || !sel) return fail(CABINET_ERR_INVALID_ARG, "ohem_select: null tensor pointer");
+    CABINET_REQUIRE_ALIGNED("ohem_select", loss_px, labels, stats, sel, workspace);
+    const size_t need = cabinet_ohem_select_workspace_bytes(nheads, B, H, W);
+    if (!workspace || workspace_bytes < need)
+        return fail(CABINET_ERR_WORKSPACE, "ohem_select: workspace %zu < %zu bytes", workspace_bytes, need);
+    const long long P = (long long)B * H * W;
+    const float* lp[2] = {loss_px, loss_px + (nheads == 2 ? P : 0)};
+    const float* cw[2] = {class_weight_a, class_weight_b};
+    const int n_min[2] = {n_min_a, n_min_b};
+    return hip_status(cabinet::ohem_select_run(nheads, lp, labels, stats, P, C, thresh, n_min, ignore_lb, cw, sel, workspace,
+                                               static_cast<hipStream_t>(stream)),
+                      "ohem_select launch");
+}
+
+int cabinet_ohem_up_w_bwd_sel(const float* logits_low, const long long* labels, const float* loss_px, int B, int C, int Hl,
+                              int Wl, int H, int W, const double* sel, int ignore_lb, float coef, float* dlogits_low,
+                              void* workspace, size_t workspace_bytes, const float* class_weight, cabinet_stream_t stream) {
+    if (int rc = check_ohem(B, C, Hl, Wl, H, W)) return rc;
+    if (!logits_low || !labels || !loss_px || !dlogits_low || !sel)
+        return fail(CABINET_ERR_INVALID_ARG, "ohem_up_bwd_sel: null tensor pointer");
+    CABINET_REQUIRE_ALIGNED("ohem_up_bwd_sel", logits_low, labels, loss_px, dlogits_low, sel);
+    const size_t need = cabinet_ohem_up_bwd_workspace_bytes(B, C, Hl, Wl, H, W);
+    if (!workspace || workspace_bytes < need)
+        return fail(CABINET_ERR_WORKSPACE, "ohem_up_bwd_sel: workspace %zu < %zu bytes", workspace_bytes, need);
+    return hip_status(cabinet::ohem_up_bwd_run(1, &logits_low, labels, &loss_px, B, C, Hl, Wl, H, W, 0.f, ignore_lb, coef,
+                                               dlogits_low, workspace, &class_weight, sel, static_cast<hipStream_t>(stream)),
+                      "ohem_up_bwd_sel launch");
+}
+
+int cabinet_ohem_up_pair_w_bwd_sel(const float* logits_low_a, const float* logits_low_b, const long long* labels,
+                                   const float* loss_px, int B, int C, int Hl, int Wl, int H, int W, const double* sel,
+                                   int ignore_lb, float coef, float* dlogits_low, void* workspace, size_t workspace_bytes,
+                                   const float* class_weight_a, const float* class_weight_b, cabinet_stream_t stream) {
+    if (int rc = check_ohem(B, C, Hl, Wl, H, W)) return rc;
+    if (!logits_low_a || !logits_low_b || !labels || !loss_px || !dlogits_low || !sel)
+        return fail(CABINET_ERR_INVALID_ARG, "ohem_up_pair_bwd_sel: null tensor pointer");
+    CABINET_REQUIRE_ALIGNED("ohem_up_pair_bwd_sel", logits_low_a, logits_low_b, labels, loss_px, dlogits_low, sel);
+    const size_t need = cabinet_ohem_up_pair_bwd_workspace_bytes(B, C, Hl, Wl, H, W);
+    if (!workspace || workspace_bytes < need)
+        return fail(CABINET_ERR_WORKSPACE, "ohem_up_pair_bwd_sel: workspace %zu < %zu bytes", workspace_bytes, need);
+    const float* low[2] = {logits_low_a, logits_low_b};
+    const float* lp[2] = {loss_px, loss_px + (size_t)B * H * W};
+    const float* cw[2] = {class_weight_a, class_weight_b};
+    return hip_status(cabinet::ohem_up_bwd_run(2, low, labels, lp, B, C, Hl, Wl, H, W, 0.f, ignore_lb, coef, dlogits_low,
+                                               workspace, cw, sel, static_cast<hipStream_t>(stream)),
+                      "ohem_up_pair_bwd_sel launch");
 }
 
 // ------------------------------------------------------ CAB local branch + block output

@@ -376,11 +376,14 @@ struct OhemBwdHeads {
     float* T[2];
 };
 
-template <int CMAX, bool EXACT, int FR, bool WT>
+// DS (device selection): the threshold is not a host scalar but row `head` of sel (nheads,4) double = [t, tie, denom, value]
+// written by the selection kernels below (ohem_select_run): a pixel counts with factor 1 when l > t, `tie` when l == t, else 0,
+// and that factor rides on the per-pixel class-weight factor cf.  DS = false is the code as it was (`thresh` by value).
+template <int CMAX, bool EXACT, int FR, bool WT, bool DS>
 __global__ __launch_bounds__(OBX_T) void ohem_up_bwd_x_kernel(OhemBwdHeads hd, const long long* __restrict__ labels, int NH, int B,
                                                              int C, int Hl, int Wl, int H, int W, float rh, float rw, float thresh,
                                                              int ignore_lb, float coef, int SX, int nox_max, int R_,
-                                                             int gplane, OhemWeights cw) {
+                                                             int gplane, OhemWeights cw, const double* __restrict__ dsel) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int R = FR ? FR : R_;
     const int nseg = (Wl + SX - 1) / SX, items = nseg * H * B, per_xcd = (items + 7) >> 3;
@@ -389,6 +392,8 @@ __global__ __launch_bounds__(OBX_T) void ohem_up_bwd_x_kernel(OhemBwdHeads hd, c
     const float* __restrict__ low = hd.low[head];
     const float* __restrict__ loss_px = hd.loss_px[head];
     float* __restrict__ T = hd.T[head];
+    float tie = 0.f;
+    if constexpr (DS) thresh = (float)dsel[4 * head], tie = (float)dsel[4 * head + 1];  // t is an fp32 value held in a double
     const int seg = item % nseg, row = item / nseg, oy = row % H, b = row / H, xs0 = seg * SX, P = H * W;
     const int nxs = min(SX, Wl - xs0);
     // output pixels whose taps can touch [xs0, xs0 + nxs)
@@ -435,7 +440,14 @@ __global__ __launch_bounds__(OBX_T) void ohem_up_bwd_x_kernel(OhemBwdHeads hd, c
             const size_t pix = (size_t)b * P + (size_t)oy * W + ox;
             lb = labels[pix];
             loss = loss_px[pix];
-            if constexpr (WT) {
+            if constexpr (DS) {
+                float wl = 1.f;
+                if constexpr (WT) wl = (lb >= 0 && lb < (long long)C) ? sw[(int)lb] : 1.f;
+                const float l = WT ? ohem_weighted(wl, loss) : loss;
+                const float f = l > thresh ? 1.f : (l == thresh ? tie : 0.f);  // after the compare: -0.0 == +0.0 as in the keys
+                sel = lb != (long long)ignore_lb && f > 0.f;
+                cf = WT ? (coef * wl) * f : coef * f;
+            } else if constexpr (WT) {
                 const float wl = (lb >= 0 && lb < (long long)C) ? sw[(int)lb] : 1.f;
                 sel = lb != (long long)ignore_lb && ohem_weighted(wl, loss) > thresh;
                 cf = coef * wl;
@@ -521,10 +533,13 @@ __global__ __launch_bounds__(OBX_T) void ohem_up_bwd_x_kernel(OhemBwdHeads hd, c
 // WT: the head's class weights live in ONE register per lane (lane c holds w[c], C <= 32) and phase 1 fetches w[label] with a
 // wave shuffle -- no LDS beyond the unweighted kernel's (C = 30 at Wl = 128 fills all 64 KB).  Every wave that runs phase 1 runs
 // it with all 64 lanes (Wl is a multiple of 64), so the lanes the shuffle reads from are active.
-template <int IPL, bool WT>
+// DS: as in the segment kernel -- [t, tie] of the head come from sel on the device; the factor f in {1, tie} multiplies the
+// class weight (lse - log2(w f) in the shift, w f (1 - lam) in the one-hot sums; f = 1 leaves both products as they were).
+template <int IPL, bool WT, bool DS>
 __global__ __launch_bounds__(256) void ohem_up_bwd_x8row_kernel(OhemBwdHeads hd, const long long* __restrict__ labels, int NH,
                                                                 int B, int C, int Hl, int H, float rh, float thresh,
-                                                                int ignore_lb, float coef, OhemWeights cw) {
+                                                                int ignore_lb, float coef, OhemWeights cw,
+                                                                const double* __restrict__ dsel) {
     constexpr int Wl = 64 * IPL, W = 8 * Wl;
     extern __shared__ __attribute__((aligned(16))) float smem[];
     float* v = smem;                 // [C][Wl]  vertically interpolated logits of this output row, exp2 domain
@@ -539,6 +554,8 @@ __global__ __launch_bounds__(256) void ohem_up_bwd_x8row_kernel(OhemBwdHeads hd,
     const float* __restrict__ low = hd.low[head];
     const float* __restrict__ loss_px = hd.loss_px[head];
     float* __restrict__ T = hd.T[head];
+    float tie = 0.f;
+    if constexpr (DS) thresh = (float)dsel[4 * head], tie = (float)dsel[4 * head + 1];
     float wreg = 1.f;  // lane c: w[c]
     if constexpr (WT) {
         const float* wp = cw.w[head];
@@ -598,14 +615,23 @@ __global__ __launch_bounds__(256) void ohem_up_bwd_x8row_kernel(OhemBwdHeads hd,
             const bool inrange = lb[j] >= 0 && lb[j] < (long long)C;
             float wl = 1.f;
             if constexpr (WT) wl = __shfl(wreg, inrange ? (int)lb[j] : 0, 64);
-            const bool sel = lb[j] != (long long)ignore_lb && (WT ? ohem_weighted(wl, ls[j]) : ls[j]) > thresh;
+            bool sel;
+            if constexpr (DS) {
+                const float l = WT ? ohem_weighted(wl, ls[j]) : ls[j];
+                const float f = l > thresh ? 1.f : (l == thresh ? tie : 0.f);
+                sel = lb[j] != (long long)ignore_lb && f > 0.f;
+                wl = WT ? wl * f : f;  // from here on the pixel's factor is w f
+            } else {
+                sel = lb[j] != (long long)ignore_lb && (WT ? ohem_weighted(wl, ls[j]) : ls[j]) > thresh;
+            }
+            constexpr bool WF = WT || DS;
             const int lrow = inrange ? (int)lb[j] * Wl : 0;
             const float* vl = v + lrow;
             const float xl = j < 4 ? fmaf(t, vl[g] - vl[gm], vl[g]) : fmaf(t, vl[gp] - vl[g], vl[g]);  // the forward's x_label
             // WT: w exp2(x - lse) = exp2(x - (lse - log2 w)); v_log_f32(1) = 0 exactly, w = 0 gives +inf (pixel switched off)
-            out[j] = sel ? (WT ? fmaf(ls[j], LOG2E_F, xl) - fast_log2(wl) : fmaf(ls[j], LOG2E_F, xl)) : INFINITY;
+            out[j] = sel ? (WF ? fmaf(ls[j], LOG2E_F, xl) - fast_log2(wl) : fmaf(ls[j], LOG2E_F, xl)) : INFINITY;
             if (sel && inrange) {  // one-hot part: this thread owns column g of every class row (j ascending: a fixed order)
-                const float a = WT ? wl * (1.f - lam) : 1.f - lam, bq = WT ? wl * lam : lam;
+                const float a = WF ? wl * (1.f - lam) : 1.f - lam, bq = WF ? wl * lam : lam;
                 if (j < 4) {
                     ohL[lrow + g] += a;
                     ohM[lrow + g] += bq;
@@ -1026,7 +1052,7 @@ static bool os_row_kernel_enabled() {
 // the forward that wrote loss_px was given: the selection is re-evaluated from them)
 hipError_t ohem_up_bwd_run(int nh, const float* const* low, const long long* labels, const float* const* loss_px, int B, int C,
                            int Hl, int Wl, int H, int W, float thresh, int ignore_lb, float coef, float* dlow, void* ws,
-                           const float* const* cw, hipStream_t stream) {
+                           const float* const* cw, const double* dsel, hipStream_t stream) {
     const OhemWeights wts{{cw ? cw[0] : nullptr, (cw && nh == 2) ? cw[1] : nullptr}};
     const bool wt = wts.w[0] || wts.w[1];
     float* T = static_cast<float*>(ws);
@@ -1054,7 +1080,7 @@ hipError_t ohem_up_bwd_run(int nh, const float* const* low, const long long* lab
     const size_t lds_band = ((size_t)6 * C * Wl + (size_t)W) * sizeof(float);
     static const auto band_enabled = [] { const char* e = getenv("CABINET_OHEM_BAND"); return e && e[0] == '1'; };
     if ((ipl == 1 || ipl == 2 || ipl == 4) && aligned && lds_band <= 64 * 1024 && H == 8 * Hl && C <= 32 && os_row_kernel_enabled() &&
-        band_enabled() && (reinterpret_cast<uintptr_t>(dlow) & 15) == 0) {
+        band_enabled() && !dsel && (reinterpret_cast<uintptr_t>(dlow) & 15) == 0) {
         const int bgrid = 8 * nh * ceil_div((Hl + 1) * B, 8);
         static lds_attr_mask b1{0}, b2{0}, b4{0}, bw1{0}, bw2{0}, bw4{0};
 #define OHEM_BAND_(I, WTV, M)                                                                                            \
@@ -1082,41 +1108,46 @@ hipError_t ohem_up_bwd_run(int nh, const float* const* low, const long long* lab
     if ((ipl == 1 || ipl == 2 || ipl == 4) && aligned && lds_row <= 64 * 1024 && os_row_kernel_enabled()) {
         const int rgrid = 8 * nh * ceil_div(H * B, 8);
         static lds_attr_mask m1{0}, m2{0}, m4{0}, mw1{0}, mw2{0}, mw4{0};
-#define OHEM_ROW_(I, WTV, M)                                                                                             \
+        static lds_attr_mask d1{0}, d2{0}, d4{0}, dw1{0}, dw2{0}, dw4{0};  // the device-selection instantiations
+#define OHEM_ROW_(I, WTV, DSV, M)                                                                                        \
         do {                                                                                                             \
-            if (hipError_t e = ensure_dynamic_lds(reinterpret_cast<const void*>(ohem_up_bwd_x8row_kernel<I, WTV>), 64 * 1024, M); \
+            if (hipError_t e = ensure_dynamic_lds(reinterpret_cast<const void*>(ohem_up_bwd_x8row_kernel<I, WTV, DSV>), 64 * 1024, M); \
                 e != hipSuccess)                                                                                         \
                 return e;                                                                                                \
-            hipLaunchKernelGGL((ohem_up_bwd_x8row_kernel<I, WTV>), dim3(rgrid), dim3(256), lds_row, stream, hd, labels, nh, B, C, \
-                               Hl, H, (float)Hl / (float)H, thresh, ignore_lb, coef, wts);                               \
+            hipLaunchKernelGGL((ohem_up_bwd_x8row_kernel<I, WTV, DSV>), dim3(rgrid), dim3(256), lds_row, stream, hd, labels, nh, B, \
+                               C, Hl, H, (float)Hl / (float)H, thresh, ignore_lb, coef, wts, dsel);                      \
         } while (0)
-#define OHEM_ROW(I, M, MW)                                                                                               \
+#define OHEM_ROW(I, M, MW, D, DW)                                                                                        \
         do {                                                                                                             \
-            if (wt) OHEM_ROW_(I, true, MW);                                                                              \
-            else OHEM_ROW_(I, false, M);                                                                                 \
+            if (dsel && wt) OHEM_ROW_(I, true, true, DW);                                                                \
+            else if (dsel) OHEM_ROW_(I, false, true, D);                                                                 \
+            else if (wt) OHEM_ROW_(I, true, false, MW);                                                                  \
+            else OHEM_ROW_(I, false, false, M);                                                                          \
         } while (0)
-        if (ipl == 1) OHEM_ROW(1, m1, mw1);
-        else if (ipl == 2) OHEM_ROW(2, m2, mw2);
-        else OHEM_ROW(4, m4, mw4);
+        if (ipl == 1) OHEM_ROW(1, m1, mw1, d1, dw1);
+        else if (ipl == 2) OHEM_ROW(2, m2, mw2, d2, dw2);
+        else OHEM_ROW(4, m4, mw4, d4, dw4);
 #undef OHEM_ROW
 #undef OHEM_ROW_
     } else {
         const size_t lds_x = lds + (wt ? OHEM_WT_LDS : 0);  // the segment's buffers stop at 60 KB
-#define OHEM_BWD_(CM, EX, WTV)                                                                                           \
+#define OHEM_BWD_(CM, EX, WTV, DSV)                                                                                      \
     do {                                                                                                                 \
         if (x8)                                                                                                          \
-            hipLaunchKernelGGL((ohem_up_bwd_x_kernel<CM, EX, 8, WTV>), dim3(xgrid), dim3(OBX_T), lds_x, stream,          \
+            hipLaunchKernelGGL((ohem_up_bwd_x_kernel<CM, EX, 8, WTV, DSV>), dim3(xgrid), dim3(OBX_T), lds_x, stream,     \
                                hd, labels, nh, B, C, Hl, Wl, H, W, (float)Hl / (float)H, (float)Wl / (float)W, thresh,   \
-                               ignore_lb, coef, SX, nox_max, R, gplane, wts);                                             \
+                               ignore_lb, coef, SX, nox_max, R, gplane, wts, dsel);                                       \
         else                                                                                                             \
-            hipLaunchKernelGGL((ohem_up_bwd_x_kernel<CM, EX, 0, WTV>), dim3(xgrid), dim3(OBX_T), lds_x, stream,          \
+            hipLaunchKernelGGL((ohem_up_bwd_x_kernel<CM, EX, 0, WTV, DSV>), dim3(xgrid), dim3(OBX_T), lds_x, stream,     \
                                hd, labels, nh, B, C, Hl, Wl, H, W, (float)Hl / (float)H, (float)Wl / (float)W, thresh,   \
-                               ignore_lb, coef, SX, nox_max, R, gplane, wts);                                             \
+                               ignore_lb, coef, SX, nox_max, R, gplane, wts, dsel);                                       \
     } while (0)
 #define OHEM_BWD(CM, EX)                                                                                                 \
     do {                                                                                                                 \
-        if (wt) OHEM_BWD_(CM, EX, true);                                                                                 \
-        else OHEM_BWD_(CM, EX, false);                                                                                   \
+        if (dsel && wt) OHEM_BWD_(CM, EX, true, true);                                                                   \
+        else if (dsel) OHEM_BWD_(CM, EX, false, true);                                                                   \
+        else if (wt) OHEM_BWD_(CM, EX, true, false);                                                                     \
+        else OHEM_BWD_(CM, EX, false, false);                                                                            \
     } while (0)
     if (C == 8) OHEM_BWD(8, true);
     else if (C == 19) OHEM_BWD(19, true);
@@ -1179,5 +1210,246 @@ hipError_t ohem_stats_run(const float* blk_sum, const int* blk_cnt, int nheads, 
     hipLaunchKernelGGL(ohem_stats_kernel, dim3(nheads), dim3(256), 0, stream, blk_sum, blk_cnt, nblk, stats);
     return hipGetLastError();
 }
+
+// ---------------------------------------------------------------------------------------------------------------------
+// The other OHEM branch on the device (reference loss.py:76-79: fewer than n_min pixels above thresh -> the n_min hardest).
+// Per head, over the valid pixels, l = w[label] * loss_px (ohem_weighted, the forward's product), k = min(n_min, n_valid):
+//   n_above >= k : t = thresh, tie = 0, denom = n_above, value = sum_above / n_above            (the row of stats, copied)
+//   else         : t = k-th largest l, n_gt = #(l > t), n_eq = #(l == t), tie = (k - n_gt) / n_eq, denom = k,
+//                  value = (sum_gt + (k - n_gt) t) / k
+// sel (nheads,4) double = [t, tie, denom, value] is what the DS backward kernels and the loss read -- no host read in between.
+//
+// t is found by a most-significant-digit radix select over order-preserving 32-bit keys of l, digits of 11 + 11 + 10 bits:
+//   init             k and `active` per head from stats (device data), histograms zeroed
+//   3 x (hist, scan) hist: every workgroup walks a contiguous chunk of pixels, ALL heads per pixel (the 8-byte label is read
+//                    once), counts the digit of the keys that match the prefix found so far in an LDS histogram (integer LDS
+//                    atomics) and adds its non-zero bins to the head's global histogram (integer atomics: order-free, exact);
+//                    scan: one workgroup per head walks the 2048 bins from the top to the bin that holds the k-th key
+//   sum              per-workgroup double sums of l over key > key(t), one slot per (head, workgroup)
+//   final            adds the slots in ascending order (fixed tree) and writes the row
+// A head on the first branch (or without a valid pixel) is inactive: its pixels cost one uniform branch per workgroup, and a
+// launch in which no head is active returns after reading 2 bytes per workgroup.  Integer counts and ordered double sums only:
+// bit-reproducible.  Traffic per pass and pixel: 8 (label) + 4 per active head; see DESIGN.md for the arithmetic.
+constexpr int OSEL_T = 256;          // threads per workgroup
+constexpr int OSEL_BINS = 2048;      // widest digit (11 bits)
+constexpr int OSEL_MAX_WG = 2048;    // workgroups of the pixel passes (and slots of the sum pass per head)
+
+struct OhemSelState {                // one per head, device memory
+    unsigned prefix;                 // the digits of key(t) found so far (right-aligned)
+    int active;                      // 1: this head needs the order statistic
+    long long k, krem;               // k; and how many of the keys inside the current prefix are still to be taken from the top
+    long long n_eq;                  // #(key == key(t)) after the last scan
+};
+
+// fp32 -> unsigned, ascending with the value for every finite float; -0.0 and +0.0 share a key
+__device__ __forceinline__ unsigned ohem_key(float l) {
+    unsigned u = __float_as_uint(l);
+    if ((u << 1) == 0u) u = 0u;
+    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+__device__ __forceinline__ float ohem_unkey(unsigned key) {
+    return __uint_as_float((key & 0x80000000u) ? (key ^ 0x80000000u) : ~key);
+}
+
+struct OhemSelHeads {
+    const float* loss_px[2];
+    const float* w[2];
+};
+
+// digit p of a key and the prefix it must match: widths 11, 11, 10 from the top
+__device__ __forceinline__ int osel_shift(int pass) { return pass == 0 ? 21 : (pass == 1 ? 10 : 0); }
+__device__ __forceinline__ int osel_bins(int pass) { return pass == 2 ? 1024 : 2048; }
+
+__global__ __launch_bounds__(OSEL_T) void ohem_sel_init_kernel(const double* __restrict__ stats, int nheads, int n_min_a, int n_min_b,
+                                                                OhemSelState* __restrict__ st, unsigned* __restrict__ hist) {
+    const int hh = blockIdx.x;
+    for (int i = threadIdx.x; i < 3 * OSEL_BINS; i += OSEL_T) hist[(size_t)hh * 3 * OSEL_BINS + i] = 0u;
+    if (threadIdx.x == 0) {
+        const long long n_valid = (long long)stats[3 * hh], n_above = (long long)stats[3 * hh + 1];
+        const long long n_min = hh == 0 ? n_min_a : n_min_b;
+        const long long k = n_min < n_valid ? n_min : n_valid;
+        OhemSelState s;
+        s.prefix = 0u;
+        s.k = k, s.krem = k, s.n_eq = 0;
+        s.active = (n_valid > 0 && k > 0 && n_above < k) ? 1 : 0;   // n_valid < 0 (a bad label): inactive, the caller raises
+        st[hh] = s;
+    }
+}
+
+// MODE 0: histogram of digit `pass`; MODE 1: double sums of l over key > key(t)
+template <int MODE>
+__global__ __launch_bounds__(OSEL_T) void ohem_sel_pass_kernel(OhemSelHeads hd, const long long* __restrict__ labels, int nheads,
+                                                                long long P, int C, int ignore_lb, int pass,
+                                                                const OhemSelState* __restrict__ st, unsigned* __restrict__ hist,
+                                                                double* __restrict__ part) {
+    __shared__ unsigned s_h[MODE == 0 ? 2 * OSEL_BINS : 1];
+    __shared__ double s_d[MODE == 1 ? 2 * (OSEL_T / 64) : 1];
+    __shared__ float s_w[2][32];
+    bool act[2];
+    unsigned prefix[2];
+#pragma unroll
+    for (int hh = 0; hh < 2; ++hh) {
+        act[hh] = hh < nheads && st[hh].active != 0;
+        prefix[hh] = act[hh] ? st[hh].prefix : 0u;
+    }
+    if (!act[0] && !act[1]) return;  // workgroup-uniform: every head is on the first branch
+    const int shift = osel_shift(pass), nb = osel_bins(pass), pshift = pass == 0 ? 0 : osel_shift(pass - 1);
+    if constexpr (MODE == 0)
+        for (int i = threadIdx.x; i < 2 * OSEL_BINS; i += OSEL_T) s_h[i] = 0u;
+    if (threadIdx.x < 64) {
+        const int hh = threadIdx.x >> 5, c = threadIdx.x & 31;
+        s_w[hh][c] = (hh < nheads && hd.w[hh] && c < C) ? hd.w[hh][c] : 1.f;
+    }
+    __syncthreads();
+    // a contiguous chunk per workgroup, whole multiples of the workgroup's stride so that chunk borders stay aligned
+    const long long per = ((P + gridDim.x - 1) / gridDim.x + OSEL_T - 1) / OSEL_T * OSEL_T;
+    const long long lo = (long long)blockIdx.x * per, hi = lo + per < P ? lo + per : P;
+    double acc[2] = {0.0, 0.0};
+    for (long long i = lo + threadIdx.x; i < hi; i += OSEL_T) {
+        const long long lb = labels[i];
+        if (lb == (long long)ignore_lb) continue;   // ignored pixels are excluded by LABEL (their loss_px is 0, a real key)
+        const int cls = (lb >= 0 && lb < (long long)C) ? (int)lb : -1;
+#pragma unroll
+        for (int hh = 0; hh < 2; ++hh) {
+            if (!act[hh]) continue;
+            const float loss = hd.loss_px[hh][i];
+            const float l = hd.w[hh] ? ohem_weighted(cls >= 0 ? s_w[hh][cls] : 1.f, loss) : loss;
+            const unsigned key = ohem_key(l);
+            if constexpr (MODE == 0) {
+                const bool in = pass == 0 || (key >> pshift) == prefix[hh];
+                if (in) atomicAdd(&s_h[hh * OSEL_BINS + ((key >> shift) & (unsigned)(nb - 1))], 1u);
+            } else {
+                if (key > prefix[hh]) acc[hh] += (double)l;
+            }
+        }
+    }
+    if constexpr (MODE == 0) {
+        __syncthreads();
+        for (int i = threadIdx.x; i < 2 * OSEL_BINS; i += OSEL_T) {
+            const int hh = i / OSEL_BINS, b = i - hh * OSEL_BINS;
+            const unsigned c = s_h[i];
+            if (c && b < nb) atomicAdd(&hist[((size_t)hh * 3 + pass) * OSEL_BINS + b], c);
+        }
+    } else {
+        // fixed order: lanes by xor-shuffle tree, waves in ascending order
+#pragma unroll
+        for (int hh = 0; hh < 2; ++hh) {
+            double v = acc[hh];
+#pragma unroll
+            for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
+            if ((threadIdx.x & 63) == 0) s_d[hh * (OSEL_T / 64) + (threadIdx.x >> 6)] = v;
+        }
+        __syncthreads();
+        if (threadIdx.x < 2 && act[threadIdx.x]) {
+            const int hh = threadIdx.x;
+            double v = 0.0;
+            for (int w = 0; w < OSEL_T / 64; ++w) v += s_d[hh * (OSEL_T / 64) + w];
+            part[(size_t)hh * OSEL_MAX_WG + blockIdx.x] = v;
+        }
+    }
+}
+
+// one workgroup per head: the bin (from the top) in which the running count reaches krem
+__global__ __launch_bounds__(OSEL_T) void ohem_sel_scan_kernel(int pass, OhemSelState* __restrict__ st, const unsigned* __restrict__ hist) {
+    __shared__ long long s_c[OSEL_T + 1];
+    const int hh = blockIdx.x, t = threadIdx.x;
+    if (!st[hh].active) return;
+    const int nb = osel_bins(pass), per = nb / OSEL_T;   // 8 or 4 consecutive bins per thread
+    const unsigned* h = hist + ((size_t)hh * 3 + pass) * OSEL_BINS;
+    const long long krem = st[hh].krem;
+    const unsigned prefix = st[hh].prefix;
+    unsigned mine[8];
+    long long sum = 0;
+    for (int u = 0; u < per; ++u) mine[u] = h[t * per + u], sum += mine[u];
+    s_c[t] = sum;
+    if (t == 0) s_c[OSEL_T] = 0;
+    __syncthreads();
+    for (int o = 1; o < OSEL_T; o <<= 1) {   // inclusive suffix sums: s_c[t] = keys in the bins of threads >= t
+        const long long add = t + o < OSEL_T ? s_c[t + o] : 0;
+        __syncthreads();
+        s_c[t] += add;
+        __syncthreads();
+    }
+    const long long above = s_c[t + 1];      // keys in higher bins than mine
+    if (s_c[t] >= krem && above < krem) {    // exactly one thread: the suffix sums fall monotonically and s_c[0] >= krem >= 1
+        long long cum = above;
+        int u = per - 1;
+        for (; u > 0; --u) {
+            if (cum + mine[u] >= krem) break;
+            cum += mine[u];
+        }
+        const int bits = pass == 2 ? 10 : 11;
+        st[hh].prefix = (prefix << bits) | (unsigned)(t * per + u);
+        st[hh].krem = krem - cum;            // to be taken from inside this bin
+        st[hh].n_eq = mine[u];               // after the last pass: the keys equal to key(t)
+    }
+}
+
+__global__ __launch_bounds__(OSEL_T) void ohem_sel_final_kernel(const double* __restrict__ stats, const OhemSelState* __restrict__ st,
+                                                                 const double* __restrict__ part, int nwg, float thresh,
+                                                                 double* __restrict__ sel) {
+    __shared__ double s_s[OSEL_T];
+    const int hh = blockIdx.x, t = threadIdx.x;
+    const OhemSelState s = st[hh];
+    if (!s.active) {
+        if (t == 0) {
+            const double n_valid = stats[3 * hh], n_above = stats[3 * hh + 1], sum_above = stats[3 * hh + 2];
+            const bool ok = n_valid > 0.0 && n_above > 0.0;
+            sel[4 * hh] = (double)thresh, sel[4 * hh + 1] = 0.0;
+            sel[4 * hh + 2] = ok ? n_above : 1.0;           // a head without a selected pixel: value 0, and a finite 1 / denom
+            sel[4 * hh + 3] = ok ? sum_above / n_above : 0.0;
+        }
+        return;
+    }
+    double v = 0.0;
+    for (int i = t; i < nwg; i += OSEL_T) v += part[(size_t)hh * OSEL_MAX_WG + i];
+    s_s[t] = v;
+    __syncthreads();
+    for (int o = OSEL_T / 2; o >= 1; o >>= 1) {
+        if (t < o) s_s[t] += s_s[t + o];
+        __syncthreads();
+    }
+    if (t == 0) {
+        const double tv = (double)ohem_unkey(s.prefix), take = (double)s.krem, k = (double)s.k;   // krem = k - n_gt
+        sel[4 * hh] = tv;
+        sel[4 * hh + 1] = take / (double)s.n_eq;
+        sel[4 * hh + 2] = k;
+        sel[4 * hh + 3] = (s_s[0] + take * tv) / k;
+    }
+}
+
+static int ohem_select_wgs(long long P) {
+    const long long want = (P + 4 * OSEL_T - 1) / (4 * OSEL_T);   // at least four strides of pixels per workgroup
+    return (int)(want < 1 ? 1 : (want > OSEL_MAX_WG ? OSEL_MAX_WG : want));
+}
+
+size_t ohem_select_workspace(int nheads) {
+    return align_up((size_t)nheads * sizeof(OhemSelState), 256) + align_up((size_t)nheads * 3 * OSEL_BINS * sizeof(unsigned), 256) +
+           align_up((size_t)nheads * OSEL_MAX_WG * sizeof(double), 256);
+}
+
+// loss_px[i] (P pixels each), labels (P), stats (nheads,3) and sel (nheads,4) on the device; n_min per head on the host
+hipError_t ohem_select_run(int nheads, const float* const* loss_px, const long long* labels, const double* stats, long long P, int C,
+                           float thresh, const int* n_min, int ignore_lb, const float* const* cw, double* sel, void* ws,
+                           hipStream_t stream) {
+    char* base = static_cast<char*>(ws);
+    OhemSelState* st = reinterpret_cast<OhemSelState*>(base);
+    unsigned* hist = reinterpret_cast<unsigned*>(base + align_up((size_t)nheads * sizeof(OhemSelState), 256));
+    double* part = reinterpret_cast<double*>(reinterpret_cast<char*>(hist) + align_up((size_t)nheads * 3 * OSEL_BINS * sizeof(unsigned), 256));
+    OhemSelHeads hd{};
+    for (int i = 0; i < nheads; ++i) hd.loss_px[i] = loss_px[i], hd.w[i] = cw ? cw[i] : nullptr;
+    const int nwg = ohem_select_wgs(P);
+    hipLaunchKernelGGL(ohem_sel_init_kernel, dim3(nheads), dim3(OSEL_T), 0, stream, stats, nheads, n_min[0],
+                       nheads == 2 ? n_min[1] : n_min[0], st, hist);
+    for (int pass = 0; pass < 3; ++pass) {
+        hipLaunchKernelGGL(ohem_sel_pass_kernel<0>, dim3(nwg), dim3(OSEL_T), 0, stream, hd, labels, nheads, P, C, ignore_lb, pass, st,
+                           hist, part);
+        hipLaunchKernelGGL(ohem_sel_scan_kernel, dim3(nheads), dim3(OSEL_T), 0, stream, pass, st, hist);
+    }
+    hipLaunchKernelGGL(ohem_sel_pass_kernel<1>, dim3(nwg), dim3(OSEL_T), 0, stream, hd, labels, nheads, P, C, ignore_lb, 3, st, hist, part);
+    hipLaunchKernelGGL(ohem_sel_final_kernel, dim3(nheads), dim3(OSEL_T), 0, stream, stats, st, part, nwg, thresh, sel);
+    return hipGetLastError();
+}
+
 
 }  // namespace cabinet

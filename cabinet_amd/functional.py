@@ -617,6 +617,114 @@ class _OhemUpSelectedPair(torch.autograd.Function):
         return dlow[0], dlow[1], None, None, None, None, None, None, None, None
 
 
+# ---- the top-n_min branch with the selection on the device (reference loss.py:67-80, both branches)
+
+
+def ohem_select_hip(loss_px, labels, stats, thresh, n_min, ignore_lb, n_classes, weights=None):
+    """Per head ``[t, tie, denom, value]`` (a (nheads,4) float64 device tensor) from the forward's ``loss_px`` (nheads,B,H,W)
+    and ``stats`` (nheads,3): the threshold the backward selects with, the factor of pixels exactly at it, the divisor of the
+    mean, and the mean itself -- ``thresh, 0, n_above, sum_above / n_above`` for a head with at least
+    ``min(n_min, n_valid)`` pixels above ``thresh``, else the order statistic of the ``n_min`` hardest pixels.
+    ``n_min``: one integer per head; ``weights``: per head the class weights the forward used, or None.  No host read."""
+    lib = _lib.load()
+    loss_px, labels, stats = _f32c(loss_px), _aligned(labels), stats.contiguous()
+    nheads = loss_px.shape[0]
+    if loss_px.dim() != 4 or nheads not in (1, 2) or tuple(stats.shape) != (nheads, 3) or stats.dtype != torch.float64:
+        raise RuntimeError(f"ohem_select_hip: loss_px {tuple(loss_px.shape)} / stats {tuple(stats.shape)} {stats.dtype}")
+    _, B, H, W = loss_px.shape
+    dev = loss_px.device
+    n_min = [int(n) for n in n_min]
+    weights = list(weights) if weights is not None else [None] * nheads
+    wts = [None if w is None else _f32c(w.detach().to(dev)) for w in weights] + [None]
+    for w in wts:
+        if w is not None and (w.dim() != 1 or w.shape[0] != n_classes):
+            raise RuntimeError(f"OhemCELoss: weight of shape {tuple(w.shape)} for {n_classes} classes")
+    sel = torch.empty((nheads, 4), dtype=torch.float64, device=dev)
+    ws, nbytes = _workspace(lib.cabinet_ohem_select_workspace_bytes(nheads, B, H, W), dev)
+    with torch.cuda.device(dev):
+        rc = lib.cabinet_ohem_select(_ptr(loss_px), _ptr(labels), _ptr(stats), nheads, B, int(n_classes), H, W, float(thresh),
+                                     n_min[0], n_min[-1], int(ignore_lb), _ptr(wts[0]), _ptr(wts[1]), _ptr(sel), _ptr(ws),
+                                     nbytes, _stream_handle(dev))
+    _lib.check(rc, "cabinet_ohem_select")
+    return sel
+
+
+def ohem_up_bwd_sel_hip(logits_low, labels, loss_px, size, sel, ignore_lb, coef, weight=None):
+    """ohem_up_bwd_hip with the threshold and the tie factor read on the device from ``sel`` (4,) (see ohem_select_hip)."""
+    lib = _lib.load()
+    logits_low, labels, loss_px = _f32c(logits_low), _aligned(labels), _f32c(loss_px)
+    weight = _class_weight(weight, logits_low)
+    B, C, Hl, Wl = logits_low.shape
+    H, W = size
+    dev = logits_low.device
+    dlow = torch.empty_like(logits_low)
+    ws, nbytes = _workspace(lib.cabinet_ohem_up_bwd_workspace_bytes(B, C, Hl, Wl, H, W), dev)
+    with torch.cuda.device(dev):
+        rc = lib.cabinet_ohem_up_w_bwd_sel(_ptr(logits_low), _ptr(labels), _ptr(loss_px), B, C, Hl, Wl, H, W, _ptr(sel),
+                                           int(ignore_lb), float(coef), _ptr(dlow), _ptr(ws), nbytes, _ptr(weight),
+                                           _stream_handle(dev))
+    _lib.check(rc, "cabinet_ohem_up_w_bwd_sel")
+    return dlow
+
+
+def ohem_up_pair_bwd_sel_hip(low_a, low_b, labels, loss_px, size, sel, ignore_lb, coef, weight_a=None, weight_b=None):
+    lib = _lib.load()
+    low_a, low_b, labels, loss_px = _f32c(low_a), _f32c(low_b), _aligned(labels), _f32c(loss_px)
+    weight_a, weight_b = _class_weight(weight_a, low_a), _class_weight(weight_b, low_b)
+    B, C, Hl, Wl = low_a.shape
+    H, W = size
+    dev = low_a.device
+    dlow = torch.empty((2, B, C, Hl, Wl), dtype=torch.float32, device=dev)
+    ws, nbytes = _workspace(lib.cabinet_ohem_up_pair_bwd_workspace_bytes(B, C, Hl, Wl, H, W), dev)
+    with torch.cuda.device(dev):
+        rc = lib.cabinet_ohem_up_pair_w_bwd_sel(_ptr(low_a), _ptr(low_b), _ptr(labels), _ptr(loss_px), B, C, Hl, Wl, H, W,
+                                                _ptr(sel), int(ignore_lb), float(coef), _ptr(dlow), _ptr(ws), nbytes,
+                                                _ptr(weight_a), _ptr(weight_b), _stream_handle(dev))
+    _lib.check(rc, "cabinet_ohem_up_pair_w_bwd_sel")
+    return dlow
+
+
+class _OhemUpDeviceSelected(torch.autograd.Function):
+    """Either branch of reference loss.py:67-80 for one head, decided on the device: ``sel`` (4,) = [t, tie, denom, value]
+    from ohem_select_hip.  loss = value; backward runs the adjoint kernels with the device threshold and scales by
+    g / denom, a device scalar.  Nothing data-dependent is a kernel argument: replayable from a captured hipGraph whatever
+    branch the replayed batch is on."""
+
+    @staticmethod
+    def forward(fn_ctx, logits_low, labels, loss_px, sel, size, ignore_lb, weight=None):
+        fn_ctx.save_for_backward(logits_low, labels, loss_px, sel)
+        fn_ctx.meta = (size, ignore_lb)
+        fn_ctx.weight = weight
+        return sel[3].to(torch.float32)
+
+    @staticmethod
+    def backward(fn_ctx, g):
+        logits_low, labels, loss_px, sel = fn_ctx.saved_tensors
+        size, ignore_lb = fn_ctx.meta
+        dlow = ohem_up_bwd_sel_hip(logits_low, labels, loss_px, size, sel, ignore_lb, 1.0, fn_ctx.weight)
+        return dlow * (g / sel[2]).to(torch.float32), None, None, None, None, None, None
+
+
+class _OhemUpDeviceSelectedPair(torch.autograd.Function):
+    """Both heads, any mix of branches: ``sel`` (2,4) from ONE selection sequence, ONE backward launch pair."""
+
+    @staticmethod
+    def forward(fn_ctx, low_a, low_b, labels, loss_px, sel, size, ignore_lb, weight_a=None, weight_b=None):
+        fn_ctx.save_for_backward(low_a, low_b, labels, loss_px, sel)
+        fn_ctx.meta = (size, ignore_lb)
+        fn_ctx.weights = (weight_a, weight_b)
+        return (sel[0, 3] + sel[1, 3]).to(torch.float32)
+
+    @staticmethod
+    def backward(fn_ctx, g):
+        low_a, low_b, labels, loss_px, sel = fn_ctx.saved_tensors
+        size, ignore_lb = fn_ctx.meta
+        dlow = ohem_up_pair_bwd_sel_hip(low_a, low_b, labels, loss_px, size, sel, ignore_lb, 1.0, *fn_ctx.weights)
+        scale = (g / sel[:, 2]).to(torch.float32)
+        dlow = dlow * scale.view(2, 1, 1, 1, 1)
+        return dlow[0], dlow[1], None, None, None, None, None, None, None
+
+
 # --------------------------------------------------------------------------- CAB local branch + block output (K5)
 
 

@@ -22,11 +22,14 @@ import torch.nn.functional as F
 
 
 class OhemCELoss(nn.Module):
-    def __init__(self, thresh, n_min, ignore_lb=255, weight=None):
+    def __init__(self, thresh, n_min, ignore_lb=255, weight=None, device_select=False):
         super().__init__()
         self.thresh = float(thresh)
         self.n_min = int(n_min)
         self.ignore_lb = ignore_lb
+        # device_select: on HIP tensors the fused head also runs the top-n_min branch on its kernels (cabinet_ohem_select +
+        # the `_bwd_sel` backward) instead of the composite path.  A plain attribute: no state_dict key.
+        self.device_select = bool(device_select)
         if weight is not None and not isinstance(weight, torch.Tensor):
             weight = torch.tensor(weight, dtype=torch.float32)
         self.register_buffer("weight", weight)
@@ -51,8 +54,10 @@ class OhemCELoss(nn.Module):
         into hand-written kernels on HIP tensors (``cabinet_ohem_up_fwd/bwd``): neither the (B,C,H,W) logits nor
         their log-softmax nor the per-pixel gradient are materialised.  The kernels implement the branch
         "at least n_min pixels above thresh", with or without class weights (non-negative, as the reference's ENet
-        weights are; the weight buffer is read by the kernels, it gets no gradient); the top-n_min branch, CPU tensors
-        and more than 32 classes take the composite path."""
+        weights are; the weight buffer is read by the kernels, it gets no gradient); CPU tensors and more than 32 classes
+        take the composite path, and so does the top-n_min branch unless the criterion was built with
+        ``device_select=True``: then that branch runs on the kernels too (k-th largest loss by a radix select on the device,
+        backward with a device threshold; a k-th value that is tied spreads its weight evenly over the tied pixels)."""
         prep = self._fused_launch(logits_low, labels, size)
         return self._fused_finish(prep, None)
 
@@ -80,6 +85,15 @@ class OhemCELoss(nn.Module):
     def _class_weight(self):
         return self.weight if isinstance(self.weight, torch.Tensor) else None
 
+    def _device_selected(self, low, lab, loss_px, stats, size):
+        """This head's loss with the branch decided on the device (either branch; needs a valid pixel)."""
+        from .functional import _OhemUpDeviceSelected, ohem_select_hip
+
+        w = self._class_weight()
+        sel = ohem_select_hip(loss_px.unsqueeze(0), lab, stats.view(1, 3), self.thresh, [self.n_min], self.ignore_lb,
+                              low.shape[1], [w])
+        return _OhemUpDeviceSelected.apply(low, lab, loss_px, sel[0], size, self.ignore_lb, w)
+
     def _fused_finish(self, prep, host_stats):
         logits_low, labels, size, low, lab, fwd = prep
         if fwd is not None:
@@ -96,11 +110,14 @@ class OhemCELoss(nn.Module):
             if n_above >= min(self.n_min, n_valid):
                 return _OhemUpSelected.apply(low, lab, loss_px, stats[2], stats[1], size, self.thresh, self.ignore_lb,
                                              self._class_weight())
+            if self.device_select:
+                return self._device_selected(low, lab, loss_px, stats, size)
         up = F.interpolate(logits_low, size=size, mode="bilinear", align_corners=False)
         return self.forward(up, labels)
 
     def extra_repr(self):
-        return f"thresh={self.thresh}, n_min={self.n_min}, ignore_lb={self.ignore_lb}"
+        extra = ", device_select=True" if self.device_select else ""
+        return f"thresh={self.thresh}, n_min={self.n_min}, ignore_lb={self.ignore_lb}{extra}"
 
 
 class SoftmaxFocalLoss(nn.Module):
@@ -162,10 +179,22 @@ def fused_pair_launch(crit_a, low_a, crit_b, low_b, labels, size):
     return _PairPrep((crit_a, crit_b), (low_a, low_b), labels, size, pair=(la, lb_, lab, loss_px, stats))
 
 
-def fused_pair_finish(prep, host_stats=None):
+def fused_pair_finish(prep, host_stats=None, branch=None):
     """Loss of both heads from a launched pair; ``host_stats`` = ``prep.stats.tolist()`` if the caller already read it (the
-    step's one host sync), else it is read here."""
+    step's one host sync), else it is read here.  ``branch`` (one-launch pairs only, for a caller that RECORDS the step into
+    a hipGraph and must not depend on the recording batch): ``"selected"`` = both heads on the 'n_min above thresh' branch,
+    ``"device"`` = both heads through the device selection, whatever the statistics say; nothing is read."""
     crit_a, crit_b = prep.crits
+    if branch is not None:
+        if prep.pair is None or branch not in ("selected", "device"):
+            raise RuntimeError("fused_pair_finish: `branch` needs a one-launch pair and is 'selected' or 'device'")
+        la, lb_, lab, loss_px, stats = prep.pair
+        if branch == "device":
+            return _pair_device_selected(prep)
+        from .functional import _OhemUpSelectedPair
+
+        return _OhemUpSelectedPair.apply(la, lb_, lab, loss_px, stats, prep.size, crit_a.thresh, crit_a.ignore_lb,
+                                         crit_a._class_weight(), crit_b._class_weight())
     if prep.pair is None:
         host = host_stats if host_stats is not None else [None, None]
         return crit_a._fused_finish(prep.heads[0], host[0]) + crit_b._fused_finish(prep.heads[1], host[1])
@@ -183,7 +212,9 @@ def fused_pair_finish(prep, host_stats=None):
 
         return _OhemUpSelectedPair.apply(la, lb_, lab, loss_px, stats, prep.size, crit_a.thresh, crit_a.ignore_lb,
                                          crit_a._class_weight(), crit_b._class_weight())
-    # a head on the rare top-n_min branch (or without a valid pixel): per-head paths (composite where needed)
+    if crit_a.device_select and crit_b.device_select and all(int(h[0]) > 0 for h in host):
+        return _pair_device_selected(prep)  # any mix of branches: one selection sequence, one backward launch pair
+    # a head on the top-n_min branch (or without a valid pixel): per-head paths (composite where device_select is off)
     from .functional import _OhemUpSelected
 
     total = None
@@ -194,10 +225,23 @@ def fused_pair_finish(prep, host_stats=None):
         elif ok:
             term = _OhemUpSelected.apply((la, lb_)[i], lab, loss_px[i], stats[i, 2], stats[i, 1], prep.size, crit.thresh,
                                          crit.ignore_lb, crit._class_weight())
+        elif crit.device_select:
+            term = crit._device_selected((la, lb_)[i], lab, loss_px[i], stats[i], prep.size)
         else:
             term = crit.forward(F.interpolate(low, size=prep.size, mode="bilinear", align_corners=False), prep.labels)
         total = term if total is None else total + term
     return total
+
+
+def _pair_device_selected(prep):
+    from .functional import _OhemUpDeviceSelectedPair, ohem_select_hip
+
+    crit_a, crit_b = prep.crits
+    la, lb_, lab, loss_px, stats = prep.pair
+    wa, wb = crit_a._class_weight(), crit_b._class_weight()
+    sel = ohem_select_hip(loss_px, lab, stats, crit_a.thresh, [crit_a.n_min, crit_b.n_min], crit_a.ignore_lb, la.shape[1],
+                          [wa, wb])
+    return _OhemUpDeviceSelectedPair.apply(la, lb_, lab, loss_px, sel, prep.size, crit_a.ignore_lb, wa, wb)
 
 
 def ohem_upsampled_pair(crit_a, low_a, crit_b, low_b, labels, size):

@@ -47,15 +47,18 @@ def build_model(mode="large", n_classes=8, device="cpu", seed=0, gamma=None, fre
     return net.to(device)
 
 
-def make_criteria(batch, height, width, device, thresh=DEFAULT_SCORE_THRESHOLD, ignore=DEFAULT_IGNORE_LABEL, weight=None):
+def make_criteria(batch, height, width, device, thresh=DEFAULT_SCORE_THRESHOLD, ignore=DEFAULT_IGNORE_LABEL, weight=None,
+                  device_select=False):
     """The step's two criteria.  ``weight``: per-class weights (a tensor or a sequence of ``n_classes`` floats), handed to both
-    criteria as the reference does (train.py:344-349); each criterion registers its own fp32 copy as a buffer."""
+    criteria as the reference does (train.py:344-349); each criterion registers its own fp32 copy as a buffer.
+    ``device_select``: see OhemCELoss (the top-n_min branch on the HIP kernels)."""
     n_min = max(1, batch * height * width // OHEM_DIVISOR)
     if weight is not None:
         weight = torch.as_tensor(weight, dtype=torch.float32).detach()
-        return (OhemCELoss(thresh, n_min, ignore, weight=weight.clone()).to(device),
-                OhemCELoss(thresh, n_min, ignore, weight=weight.clone()).to(device))
-    return (OhemCELoss(thresh, n_min, ignore).to(device), OhemCELoss(thresh, n_min, ignore).to(device))
+        return (OhemCELoss(thresh, n_min, ignore, weight=weight.clone(), device_select=device_select).to(device),
+                OhemCELoss(thresh, n_min, ignore, weight=weight.clone(), device_select=device_select).to(device))
+    return (OhemCELoss(thresh, n_min, ignore, device_select=device_select).to(device),
+            OhemCELoss(thresh, n_min, ignore, device_select=device_select).to(device))
 
 
 class TrainStep:
@@ -233,15 +236,30 @@ class GraphedTrainStep:
     Class weights (``criteria`` built with ``weight=``) are static tensors too: the graphs hold the ADDRESSES of the criteria's
     weight buffers, so an in-place update (``crit.weight.copy_(w)``) is seen by the next replay, while rebinding
     ``crit.weight = w`` (or ``.to()`` / ``.half()`` on the criterion) after capture is not -- build a new step for that.
-    Data-parallel runs keep the eager TrainStep: its reducer launches collectives from autograd hooks."""
+    Data-parallel runs keep the eager TrainStep: its reducer launches collectives from autograd hooks.
 
-    def __init__(self, net, criteria, optimizer=None, warmup=2, capture_optimizer=False, before_optimizer=None):
+    ``device_select=True`` (criteria built with ``device_select=True``, which it sets on them) adds a third graph:
+
+        graph B-any   device selection of both heads (cabinet_ohem_select), loss, backward with the device threshold
+
+    recorded beside graph B over the same autograd graph and replayed whenever the host read says a head is off the
+    'n_min above thresh' branch and both heads have a valid pixel -- late training, fine-tuning, a resumed run.  Graph B
+    still serves the step with both heads on that branch, bit for bit; ``fallbacks`` then counts all-ignored batches only,
+    and the capture batch may be on either branch (recording executes nothing).  B-any's backward leaves its gradients in
+    tensors of its own and ends with one multi-tensor copy into graph B's static gradient tensors, so ``.grad`` and a
+    captured optimizer step read the same addresses after either graph."""
+
+    def __init__(self, net, criteria, optimizer=None, warmup=2, capture_optimizer=False, before_optimizer=None,
+                 device_select=False):
         self.net, (self.crit_p, self.crit_16) = net, criteria
         self.optimizer, self.warmup = optimizer, warmup
+        self.device_select = bool(device_select)
+        if self.device_select:
+            self.crit_p.device_select = self.crit_16.device_select = True  # the warm-up and all-ignored steps run eagerly
         self.opt_seg = _OptimizerSegment(optimizer, capture_optimizer, before_optimizer)
         self.eager = TrainStep(net, criteria, optimizer=optimizer, before_optimizer=before_optimizer)
-        self.g_fwd = self.g_bwd = None
-        self.fallbacks = self._calls = 0
+        self.g_fwd = self.g_bwd = self.g_any = None
+        self.fallbacks = self.device_selected = self._calls = 0  # eager fallbacks / replays of graph B-any
 
     def _capture(self, im, lb):
         """Record the two graphs on this batch.  Nothing of the step executes here (capture only records), except one
@@ -262,21 +280,24 @@ class GraphedTrainStep:
             self.s_stats = self.prep.stats
             if self.s_stats is None:
                 raise RuntimeError("GraphedTrainStep needs the fused OHEM head (device logits, <= 32 classes)")
-        # capture does not execute: replay once to learn the capture batch's branch, then undo its BatchNorm side effects
-        self.snap.save()
-        self.g_fwd.replay()
-        host = self.s_stats.tolist()
-        self.snap.restore()
-        if not all(self._selected_branch(c, h) for c, h in zip((self.crit_p, self.crit_16), host)):
-            raise RuntimeError("GraphedTrainStep: capture batch does not take the OHEM 'n_min above thresh' branch; "
-                               "capture on a representative batch")
-        self.g_bwd = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(self.g_bwd, pool=self.g_fwd.pool(), capture_error_mode=_CAPTURE_MODE):
-            loss = fused_pair_finish(self.prep, host)
-            loss.backward()
-            self.s_loss = loss.detach()
+        if self.device_select:
+            self._capture_both_branches()
+        else:
+            # capture does not execute: replay once to learn the capture batch's branch, then undo its BatchNorm side effects
+            self.snap.save()
+            self.g_fwd.replay()
+            host = self.s_stats.tolist()
+            self.snap.restore()
+            if not all(self._selected_branch(c, h) for c, h in zip((self.crit_p, self.crit_16), host)):
+                raise RuntimeError("GraphedTrainStep: capture batch does not take the OHEM 'n_min above thresh' branch; "
+                                   "capture on a representative batch (or build the step with device_select=True)")
+            self.g_bwd = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(self.g_bwd, pool=self.g_fwd.pool(), capture_error_mode=_CAPTURE_MODE):
+                loss = fused_pair_finish(self.prep, host)
+                loss.backward()
+                self.s_loss = loss.detach()
+            self.s_grads = [(p, p.grad) for p in self.net.parameters() if p.grad is not None]
         self.opt_seg.record(self.g_fwd.pool())
-        self.s_grads = [(p, p.grad) for p in self.net.parameters() if p.grad is not None]
         with torch.no_grad():
             for p, g in self.s_grads:
                 if p in eager_grads:
@@ -284,6 +305,39 @@ class GraphedTrainStep:
                 else:
                     g.zero_()
         torch.cuda.synchronize()
+
+    def _capture_both_branches(self):
+        """Graph B and graph B-any over the one autograd graph of graph A.  Neither depends on the capture batch: the
+        branch is named, not read (``fused_pair_finish(branch=...)``).  The first backward retains the autograd graph for
+        the second; the second starts from ``.grad = None`` so that it does not accumulate into graph B's gradient tensors."""
+        if self.prep.pair is None:
+            raise RuntimeError("GraphedTrainStep(device_select=True) needs the one-launch pair of the OHEM head (two heads "
+                               "of one shape with one threshold and ignore label)")
+        pool = self.g_fwd.pool()
+        self.g_bwd = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(self.g_bwd, pool=pool, capture_error_mode=_CAPTURE_MODE):
+            loss = fused_pair_finish(self.prep, branch="selected")
+            loss.backward(retain_graph=True)
+            self.s_loss = loss.detach()
+        self.s_grads = [(p, p.grad) for p in self.net.parameters() if p.grad is not None]
+        for p, _ in self.s_grads:
+            p.grad = None
+        self.g_any = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(self.g_any, pool=pool, capture_error_mode=_CAPTURE_MODE):
+            loss = fused_pair_finish(self.prep, branch="device")
+            loss.backward()
+            self.s_loss_any = loss.detach()
+            dst, src = [], []
+            for p, g in self.s_grads:
+                if p.grad is None:
+                    g.zero_()
+                else:
+                    dst.append(g)
+                    src.append(p.grad)
+            if dst:
+                torch._foreach_copy_(dst, src)
+        for p, g in self.s_grads:
+            p.grad = g
 
     @staticmethod
     def _selected_branch(crit, host):
@@ -314,7 +368,15 @@ class GraphedTrainStep:
             self.g_bwd.replay()
             self.opt_seg.run()
             return self.s_loss
-        # rare branch (late training: fewer than n_min hard pixels): undo graph A's BatchNorm side effects, run eagerly
+        if self.g_any is not None and all(int(h[0]) > 0 for h in host):  # a head on the top-n_min branch: graph B-any
+            self.device_selected += 1
+            for p, g in self.s_grads:
+                p.grad = g
+            self.g_any.replay()
+            self.opt_seg.run()
+            return self.s_loss_any
+        # a head on the top-n_min branch without device_select (late training: fewer than n_min hard pixels), or a batch
+        # without a valid pixel: undo graph A's BatchNorm side effects, run eagerly
         self.fallbacks += 1
         self.snap.restore()
         loss = self.eager(im, lb)
@@ -386,7 +448,9 @@ class GraphedDDPStep:
         eager      optimizer step (_OptimizerSegment: host-side schedules / clipping; opt-in graph for constant lr)
 
     Collectives are ordinary eager calls between replays (nothing of RCCL is captured), always the same buckets in the
-    same order on every rank, also on a rank that falls back to the eager path for this step (rare OHEM branch).
+    same order on every rank, also on a rank that falls back to the eager path for this step (a head on the OHEM top-n_min
+    branch: GraphedTrainStep's ``device_select`` graph B-any is NOT built here, this step keeps its eager fallback; criteria
+    built with ``device_select=True`` still run that branch on the HIP kernels inside the fallback).
     Autograd writes each gradient into its own tensor (``.grad`` is None during backward, so nothing is accumulated); one
     ``torch._foreach_copy_`` per segment packs them into the flat fp32 buckets, and ``.grad`` then IS the bucket view the
     all-reduce averages and the optimizer reads.  (Pre-zeroed bucket views as ``.grad`` made autograd run one in-place add

@@ -186,7 +186,7 @@ int cabinet_ffm_up_bwd(const float* dout, const float* fsp, const float* low, co
  * Replaces src/models/cabinet.py:240-245 (F.interpolate of the (B,C,Hl,Wl) logits to (H,W), bilinear,
  * align_corners=False) + src/utils/loss.py:51-80 (per-pixel CE with ignore_index, OHEM selection, mean)
  * for the selection branch "at least n_min pixels have loss > thresh" (loss.py:74-75).  The other branch
- * (top-n_min) needs an order statistic; callers take the unfused path for it.
+ * (top-n_min) needs an order statistic: cabinet_ohem_select + the `_bwd_sel` entry points further down, or the unfused path.
  *   fwd : loss_px (B,H,W) per-pixel CE (0 at ignored pixels); per-workgroup partials
  *         blk_cnt[2*i] = #valid, blk_cnt[2*i+1] = #(loss > thresh), blk_sum[i] = sum of those losses,
  *         i < cabinet_ohem_up_blocks(B,H,W); the caller reduces them (and decides the branch)
@@ -247,6 +247,32 @@ int cabinet_ohem_up_pair_w_bwd(const float* logits_low_a, const float* logits_lo
                                const float* loss_px, int B, int C, int Hl, int Wl, int H, int W, float thresh, int ignore_lb,
                                float coef, float* dlogits_low, void* workspace, size_t workspace_bytes,
                                const float* class_weight_a, const float* class_weight_b, cabinet_stream_t stream);
+/* BOTH branches of the criterion with the branch decided ON THE DEVICE -- reference src/utils/loss.py:67-80: `if
+ * sorted_loss[n_min] > thresh: keep loss > thresh, else: keep the n_min hardest`, then the mean.  (Added under ABI v8.)
+ * Per head, over the valid pixels (label != ignore_lb), l = w[label] * loss_px (the forward's product), k = min(n_min, #valid):
+ *   #above >= k : t = thresh,            tie = 0,                      denom = #above, value = sum_above / #above
+ *   else        : t = k-th largest l,    tie = (k - #(l > t)) / #(l == t), denom = k,  value = (sum_{l > t} l + (k - #(l > t)) t) / k
+ * cabinet_ohem_select: loss_px (nheads,B,H,W) and stats (nheads,3) as the forward and cabinet_ohem_stats left them ->
+ *   sel (nheads,4) double = [t, tie, denom, value]; nheads = 1 | 2 (n_min_b, class_weight_b unused for 1).  value is loss.py's
+ *   mean of the kept losses.  An MSD radix select over order-preserving keys of l (-0.0 == +0.0); integer histograms and
+ *   ordered double sums: bit-reproducible.  k is formed on the device (#valid is data); no host read.  B*H*W < 2^31.
+ * cabinet_ohem_up[_pair]_w_bwd_sel: the `_w_bwd` argument lists with `const double* sel` (device) in place of `float thresh`:
+ *   dlogits_low = coef * U^T[ f * w[label] * (softmax - onehot) ],  f = 1 (l > t) | tie (l == t) | 0; the caller folds
+ *   upstream_grad / denom in.  With a unique k-th value this is loss.py's gradient; where the k-th value is tied the
+ *   reference keeps whichever of the tied pixels its sort put first, here the same total weight is spread evenly over them. */
+size_t cabinet_ohem_select_workspace_bytes(int nheads, int B, int H, int W);
+int cabinet_ohem_select(const float* loss_px, const long long* labels, const double* stats, int nheads,
+                        int B, int C, int H, int W, float thresh, int n_min_a, int n_min_b, int ignore_lb,
+                        const float* class_weight_a, const float* class_weight_b, double* sel,
+                        void* workspace, size_t workspace_bytes, cabinet_stream_t stream);
+int cabinet_ohem_up_w_bwd_sel(const float* logits_low, const long long* labels, const float* loss_px,
+                              int B, int C, int Hl, int Wl, int H, int W, const double* sel, int ignore_lb, float coef,
+                              float* dlogits_low, void* workspace, size_t workspace_bytes, const float* class_weight,
+                              cabinet_stream_t stream);
+int cabinet_ohem_up_pair_w_bwd_sel(const float* logits_low_a, const float* logits_low_b, const long long* labels,
+                                   const float* loss_px, int B, int C, int Hl, int Wl, int H, int W, const double* sel,
+                                   int ignore_lb, float coef, float* dlogits_low, void* workspace, size_t workspace_bytes,
+                                   const float* class_weight_a, const float* class_weight_b, cabinet_stream_t stream);
 
 /* ------------------------------------------------------------------------- *
  * CAB local branch + block output.
