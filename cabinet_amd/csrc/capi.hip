@@ -124,6 +124,14 @@ bool pwconv_wide_supported(int Ci, int Co, int P);
 size_t pwconv_wide_wgrad_workspace(int B, int Ci, int Co, int P);
 hipError_t pwconv_wide_wgrad_run(const float* dy, const float* x, int B, int Ci, int Co, int P, float* dw, void* ws,
                                  hipStream_t stream);
+// conv3x3_s2.hip
+bool conv3x3s2_supported(int Ci, int Co);
+long long conv3x3s2_wgrad_slabs(int B, int Ci, int H, int W);
+size_t conv3x3s2_wgrad_workspace(int B, int Ci, int H, int W);
+hipError_t conv3x3s2_wgrad_run(const float* dy, const float* x, int B, int Ci, int H, int W, float* dw, void* ws,
+                               hipStream_t stream);
+long long conv3x3s2_dgrad_workgroups(int B, int H, int W);
+hipError_t conv3x3s2_dgrad_run(const float* dy, const float* w, int B, int H, int W, float* dx, hipStream_t stream);
 // pwconv.hip
 bool pwconv_supported(int Ci, int Co, int P);
 size_t pwconv_bwd_workspace(int B, int Ci, int Co, int P);
@@ -1205,6 +1213,48 @@ int cabinet_pwconv_wide_wgrad(const float* dy, const float* x, int B, int Ci, in
         return fail(CABINET_ERR_WORKSPACE, "pwconv_wide_wgrad: workspace %zu < %zu bytes", workspace_bytes, need);
     return hip_status(cabinet::pwconv_wide_wgrad_run(dy, x, B, Ci, Co, P, dw, workspace, static_cast<hipStream_t>(stream)),
                       "pwconv_wide_wgrad launch");
+}
+
+// ------------------------------------------------------ 3x3 stride-2 convolution: weight and input gradient
+static bool conv3x3s2_size_ok(int B, int Ci, int H, int W) {  // the kernels index with 64 bits; the grid is one workgroup per slab
+    return cabinet::conv3x3s2_wgrad_slabs(B, Ci, H, W) <= (1ll << 30);
+}
+
+int cabinet_conv3x3s2_supported(int Ci, int Co) { return cabinet::conv3x3s2_supported(Ci, Co) ? 1 : 0; }
+
+size_t cabinet_conv3x3s2_wgrad_workspace_bytes(int B, int Ci, int Co, int H, int W) {
+    if (B <= 0 || H <= 0 || W <= 0 || !cabinet::conv3x3s2_supported(Ci, Co) || !conv3x3s2_size_ok(B, Ci, H, W)) return 0;
+    return cabinet::conv3x3s2_wgrad_workspace(B, Ci, H, W);
+}
+
+int cabinet_conv3x3s2_wgrad(const float* dy, const float* x, int B, int Ci, int Co, int H, int W, float* dw, void* workspace,
+                            size_t workspace_bytes, cabinet_stream_t stream) {
+    if (B <= 0 || Ci <= 0 || Co <= 0 || H <= 0 || W <= 0)
+        return fail(CABINET_ERR_INVALID_ARG, "conv3x3s2_wgrad: non-positive dimension");
+    if (!cabinet::conv3x3s2_supported(Ci, Co))
+        return fail(CABINET_ERR_UNSUPPORTED, "conv3x3s2_wgrad: Ci=%d, Co=%d ((64, 64) and (3, 16) are compiled)", Ci, Co);
+    if (!conv3x3s2_size_ok(B, Ci, H, W))
+        return fail(CABINET_ERR_UNSUPPORTED, "conv3x3s2_wgrad: B=%d, H=%d, W=%d: grid too large", B, H, W);
+    if (!dy || !x || !dw) return fail(CABINET_ERR_INVALID_ARG, "conv3x3s2_wgrad: null tensor pointer");
+    const size_t need = cabinet::conv3x3s2_wgrad_workspace(B, Ci, H, W);
+    if (!workspace || workspace_bytes < need)
+        return fail(CABINET_ERR_WORKSPACE, "conv3x3s2_wgrad: workspace %zu < %zu bytes", workspace_bytes, need);
+    return hip_status(cabinet::conv3x3s2_wgrad_run(dy, x, B, Ci, H, W, dw, workspace, static_cast<hipStream_t>(stream)),
+                      "conv3x3s2_wgrad launch");
+}
+
+int cabinet_conv3x3s2_dgrad(const float* dy, const float* w, int B, int Ci, int Co, int H, int W, float* dx,
+                            cabinet_stream_t stream) {
+    if (B <= 0 || Ci <= 0 || Co <= 0 || H <= 0 || W <= 0)
+        return fail(CABINET_ERR_INVALID_ARG, "conv3x3s2_dgrad: non-positive dimension");
+    if (Ci != 64 || Co != 64)
+        return fail(CABINET_ERR_UNSUPPORTED, "conv3x3s2_dgrad: Ci=%d, Co=%d ((64, 64) is compiled)", Ci, Co);
+    if (cabinet::conv3x3s2_dgrad_workgroups(B, H, W) > (1ll << 30))
+        return fail(CABINET_ERR_UNSUPPORTED, "conv3x3s2_dgrad: B=%d, H=%d, W=%d: grid too large", B, H, W);
+    if (!dy || !w || !dx) return fail(CABINET_ERR_INVALID_ARG, "conv3x3s2_dgrad: null tensor pointer");
+    if ((reinterpret_cast<size_t>(dx) & 7) != 0)
+        return fail(CABINET_ERR_INVALID_ARG, "conv3x3s2_dgrad: dx must be 8-byte aligned");
+    return hip_status(cabinet::conv3x3s2_dgrad_run(dy, w, B, H, W, dx, static_cast<hipStream_t>(stream)), "conv3x3s2_dgrad launch");
 }
 
 // ------------------------------------------------------ dense 3x3 convolution (Winograd F(2x2,3x3), fp32 MFMA)

@@ -1,0 +1,348 @@
+// K15 -- weight gradient (and, 64 -> 64, input gradient) of the 3x3 stride-2 padding-1 bias-free convolutions, NCHW fp32, no
+// layout copy.
+//
+// Serves the spatial branch's conv2 / conv3 (64 -> 64, reference src/models/cabinet.py:112-113, SpatialBranch) and the
+// backbone's first layer (3 -> 16, reference src/models/mobilenetv3.py:86-91,173, conv_3x3_bn(3, 16, 2)).  MIOpen computes these
+// weight gradients with NHWC implicit-GEMM kernels and first copies x and dy to NHWC and dw back; the product
+//     dW[co][ci][ky][kx] = sum_{b,oy,ox} dY[b][co][oy][ox] * X[b][ci][2 oy - 1 + ky][2 ox - 1 + kx]
+// contracts over pixels, the contiguous axis of BOTH operands in NCHW.  The forward stays the stock operator's.
+//
+//   64 -> 64 : a workgroup (4 waves) walks output rows oy of one 32-pixel column tile.  Per row it stages the 64 x 32 dy
+//              segment ([co][33]) and the 64 x 3 x 65 input patch ([ci][3][65]: plane pitch 195, odd, so the 32 channels on
+//              32 lanes fall on 32 banks) in LDS.  dW is 2 x 2 x 9 blocks of 32 x 32 (co half, ci half, tap); wave (i, j) owns
+//              the nine taps of its (co half, ci half): 144 accumulator registers, one A read and nine B reads ("pixel pair
+//              on h, channel on li") per nine exact-fp32 MFMA 32x32x2.  All four waves walk the same pixels and own disjoint
+//              blocks, so no cross-wave sum exists: each wave stores its blocks of the workgroup's slab.  58 KB of LDS: two
+//              workgroups per CU, one stages while the other multiplies.
+//   3 -> 16  : K9's weight-gradient form at (Ci 3, k 3, Co 16): a 4 x 32 output tile, the dy tile ([32][129], rows 16..31
+//              zero) and the 3 x 9 x 65 patch in LDS, one 32 x 32 block per wave (27 of 32 columns live), wave = tile row,
+//              ordered cross-wave sum.  234 MB of operands for 1.8 GFLOP: a streaming kernel.
+//   output   : one slab per workgroup, ordered slab sum (slab_sum.hpp): no atomics, bit-reproducible, capturable.
+//
+// Input gradient, 64 -> 64:
+//     dX[b][ci][iy][ix] = sum_{co,ky,kx} W[co][ci][ky][kx] * dY[b][co][(iy + 1 - ky) / 2][(ix + 1 - kx) / 2]
+// over the taps where both quotients are integers and in range: by the four parity classes of (iy, ix), which take 1, 2, 2 and
+// 4 taps, so no product with a structural zero is executed.  M = ci, N = the pixels of a class, K = co x taps, on the exact-fp32
+// MFMA 16x16x4: a wave owns 16 input channels and keeps their 64 x 9 weights in 144 registers for the whole kernel (the A
+// operand never touches the LDS); the workgroup stages two dy rows ([co][2][72]) per step and every wave reads its B operand
+// from them, tap by tap.  The even- and odd-column classes of one lane are neighbours in dX: a lane
+// stores them as one pair, 16 lanes as one 128-byte run.  Every element of dX is written (rows and columns past the last tap
+// included: their sums are over zero-staged dy).
+#include "common.hpp"
+#include "slab_sum.hpp"
+
+namespace cabinet {
+
+struct C3Shape {
+    int B, H, W, Ho, Wo;
+};
+
+static C3Shape c3_shape(int B, int H, int W) { return C3Shape{B, H, W, (H - 1) / 2 + 1, (W - 1) / 2 + 1}; }
+
+// ------------------------------------------------------------------------------------------------ 64 -> 64
+constexpr int CW_C = 64;                  // channels, both sides
+constexpr int CW_TW = 32;                 // output pixels of a step: one row segment
+constexpr int CW_IW = 2 * CW_TW + 1;      // 65 input columns
+constexpr int CW_XP = 3 * CW_IW;          // 195: channel pitch of the patch (odd)
+constexpr int CW_DLD = CW_TW + 1;         // 33: row stride of the dy segment
+constexpr int CW_SLAB = CW_C * CW_C * 9;  // 36864 floats
+constexpr int CW_TARGET_WG = 512;         // two resident workgroups on each of the 256 CUs
+constexpr int CW_MIN_ROWS = 4;            // a workgroup walks at least this many rows per 147 KB slab it writes
+
+struct C3Plan {
+    int tiles_x, strips, rows_per;
+};
+
+static C3Plan cw_plan(const C3Shape& s) {
+    C3Plan p;
+    p.tiles_x = ceil_div(s.Wo, CW_TW);
+    const long per = (long)s.B * p.tiles_x;
+    long strips = CW_TARGET_WG / per;
+    const int cap = ceil_div(s.Ho, CW_MIN_ROWS);
+    if (strips > cap) strips = cap;
+    if (strips < 1) strips = 1;
+    p.rows_per = ceil_div(s.Ho, (int)strips);
+    p.strips = ceil_div(s.Ho, p.rows_per);
+    return p;
+}
+
+__global__ __launch_bounds__(256, 2) void conv3x3s2_wgrad64_kernel(const float* __restrict__ dy, const float* __restrict__ x,
+                                                                 C3Shape s, int tiles_x, int strips, int rows_per,
+                                                                 float* __restrict__ slabs) {
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    float* xs = smem;                 // [64][3][65]
+    float* dys = xs + CW_C * CW_XP;   // [64][33]
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, li = lane & 31, h = lane >> 5;
+    int bi = blockIdx.x;
+    const int tx = bi % tiles_x;
+    bi /= tiles_x;
+    const int strip = bi % strips, b = bi / strips;
+    const int oy_begin = strip * rows_per, oy_end = min(s.Ho, oy_begin + rows_per);
+    const int ox0 = tx * CW_TW, ix0 = 2 * ox0 - 1;
+    const int ch = wave & 1, cj = wave >> 1;  // this wave's co half and ci half
+
+    f32x16 acc[9];
+#pragma unroll
+    for (int t = 0; t < 9; ++t)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[t][r] = 0.f;
+
+    const float* xb = x + (size_t)b * CW_C * s.H * s.W;
+    const float* dyb = dy + (size_t)b * CW_C * s.Ho * s.Wo;
+    const float* arow = dys + (32 * ch + li) * CW_DLD + h;
+    const float* brow = xs + (32 * cj + li) * CW_XP + 2 * h;
+    for (int oy = oy_begin; oy < oy_end; ++oy) {
+        const int iy0 = 2 * oy - 1;
+        __syncthreads();  // the previous row's operand reads are done
+        for (int i = tid; i < CW_C * CW_XP; i += 256) {
+            const int ci = i / CW_XP, r = i - ci * CW_XP, yy = r / CW_IW, xx = r - yy * CW_IW;
+            const int iy = iy0 + yy, ix = ix0 + xx;
+            xs[i] = (iy >= 0 && iy < s.H && ix >= 0 && ix < s.W) ? xb[((size_t)ci * s.H + iy) * s.W + ix] : 0.f;
+        }
+        for (int i = tid; i < CW_C * CW_TW; i += 256) {
+            const int co = i >> 5, c = i & 31, ox = ox0 + c;
+            dys[co * CW_DLD + c] = ox < s.Wo ? dyb[((size_t)co * s.Ho + oy) * s.Wo + ox] : 0.f;
+        }
+        __syncthreads();
+#pragma unroll
+        for (int c0 = 0; c0 < CW_TW; c0 += 2) {  // pixels c0 + h: two per MFMA
+            const float a = arow[c0];
+#pragma unroll
+            for (int ky = 0; ky < 3; ++ky)
+#pragma unroll
+                for (int kx = 0; kx < 3; ++kx)
+                    acc[3 * ky + kx] = mfma32(a, brow[ky * CW_IW + 2 * c0 + kx], acc[3 * ky + kx]);
+        }
+    }
+    // this wave's 32 x 32 x 9 part of the slab, in dW's own layout [co][ci][tap]
+    float* slab = slabs + (size_t)blockIdx.x * CW_SLAB;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+        const int co = 32 * ch + acc_row(r) + 4 * h, ci = 32 * cj + li;
+        float* p = slab + (co * CW_C + ci) * 9;
+#pragma unroll
+        for (int t = 0; t < 9; ++t) p[t] = acc[t][r];
+    }
+}
+
+// ------------------------------------------------------------------------------------------------ 3 -> 16
+constexpr int CF_CI = 3, CF_CO = 16, CF_KK = CF_CI * 9;  // 27 columns
+constexpr int CF_TH = 4, CF_TW = 32;                     // 128 pixels per step, 32 per wave
+constexpr int CF_IH = 2 * CF_TH + 1, CF_IW = 2 * CF_TW + 1;  // 9 x 65
+constexpr int CF_PATCH = CF_CI * CF_IH * CF_IW;          // 1755 floats
+constexpr int CF_DLD = CF_TH * CF_TW + 1;                // 129: row stride of the dy tile
+constexpr int CF_SLAB = CF_CO * CF_KK;                   // 432 floats
+
+__global__ __launch_bounds__(256) void conv3x3s2_wgrad_3_16_kernel(const float* __restrict__ dy, const float* __restrict__ x,
+                                                                  C3Shape s, int tiles_x, float* __restrict__ slabs) {
+    __shared__ __attribute__((aligned(16))) float dys[32 * CF_DLD];  // rows 16..31 stay zero: the A operand's upper half
+    __shared__ float xs[CF_PATCH];                                    // [3][9][65]
+    __shared__ float red[4][CF_CO][32];
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, li = lane & 31, h = lane >> 5;
+    const int strips_y = (s.Ho + CF_TH - 1) / CF_TH;
+    const int b = blockIdx.x / strips_y, oy0 = (blockIdx.x - b * strips_y) * CF_TH;
+    // patch offset of this lane's column k = li = (ci, ky, kx); columns >= 27 read offset 0 and are dropped
+    const int kk = li < CF_KK ? li : 0;
+    const int ko = ((kk / 9) * CF_IH + (kk % 9) / 3) * CF_IW + kk % 3;
+    f32x16 acc;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[r] = 0.f;
+    for (int i = tid; i < 16 * CF_DLD; i += 256) dys[16 * CF_DLD + i] = 0.f;
+    const float* xb = x + (size_t)b * CF_CI * s.H * s.W;
+    const float* dyb = dy + (size_t)b * CF_CO * s.Ho * s.Wo;
+    const int iy0 = 2 * oy0 - 1;
+    for (int t = 0; t < tiles_x; ++t) {
+        const int ox0 = t * CF_TW, ix0 = 2 * ox0 - 1;
+        __syncthreads();
+        for (int i = tid; i < CF_PATCH; i += 256) {
+            const int ci = i / (CF_IH * CF_IW), r = i - ci * CF_IH * CF_IW, yy = r / CF_IW, xx = r - yy * CF_IW;
+            const int iy = iy0 + yy, ix = ix0 + xx;
+            xs[i] = (iy >= 0 && iy < s.H && ix >= 0 && ix < s.W) ? xb[((size_t)ci * s.H + iy) * s.W + ix] : 0.f;
+        }
+        for (int i = tid; i < CF_CO * CF_TH * CF_TW; i += 256) {
+            const int co = i / (CF_TH * CF_TW), p = i - co * (CF_TH * CF_TW), r = p / CF_TW, c = p - r * CF_TW;
+            const int oy = oy0 + r, ox = ox0 + c;
+            dys[co * CF_DLD + p] = (oy < s.Ho && ox < s.Wo) ? dyb[((size_t)co * s.Ho + oy) * s.Wo + ox] : 0.f;
+        }
+        __syncthreads();
+        // this wave contracts over output row `wave` of the tile, two pixels per MFMA
+        const float* drow = dys + li * CF_DLD + 32 * wave + h;
+        const float* prow = xs + ko + 2 * wave * CF_IW + 2 * h;
+#pragma unroll
+        for (int c0 = 0; c0 < 32; c0 += 2) acc = mfma32(drow[c0], prow[2 * c0], acc);
+    }
+    // rows 0..15 of the block are registers 0..7 (acc_row(r) + 4 h < 16); the four waves' copies are added in wave order
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+        const int co = acc_row(r) + 4 * h;
+        if (co < CF_CO) red[wave][co][li] = acc[r];
+    }
+    __syncthreads();
+    float* slab = slabs + (size_t)blockIdx.x * CF_SLAB;
+    for (int i = tid; i < CF_SLAB; i += 256) {
+        const int co = i / CF_KK, k = i - co * CF_KK;
+        slab[i] = ((red[0][co][k] + red[1][co][k]) + red[2][co][k]) + red[3][co][k];
+    }
+}
+
+// ------------------------------------------------------------------------------------------------ input gradient, 64 -> 64
+typedef float f32x4v __attribute__((ext_vector_type(4)));
+// v_mfma_f32_16x16x4_f32: lane l supplies A[row = l&15][k = l>>4] and B[k = l>>4][col = l&15]; register r of lane l is
+// D[row = 4*(l>>4) + r][col = l&15]
+__device__ __forceinline__ f32x4v mfma16(float a, float b, f32x4v c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
+
+constexpr int CD_NT = 64;             // columns n of dy per step: 128 columns of dX
+constexpr int CD_RP = 72;             // row pitch of the dy tile (65 columns live)
+constexpr int CD_CP = 2 * CD_RP;      // 144: channel pitch, = 16 mod 32 (the two channels of a 32-lane read group: disjoint banks)
+
+// the tap of dY that input parity 0 (even) / 1 (odd) takes with kernel index k: even rows take k = 1 from row m; odd rows
+// take k = 0 from row m + 1 and k = 2 from row m
+__host__ __device__ constexpr int cd_par(int k) { return k == 1 ? 0 : 1; }
+__host__ __device__ constexpr int cd_shift(int k) { return k == 0 ? 1 : 0; }
+
+__global__ __launch_bounds__(256, 2) void conv3x3s2_dgrad64_kernel(const float* __restrict__ dy, const float* __restrict__ w,
+                                                                 C3Shape s, int tiles_n, int strips, int rows_per,
+                                                                 float* __restrict__ dx) {
+    __shared__ __attribute__((aligned(16))) float dys[CW_C * CD_CP];  // [co][2 rows][72]
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, lc = lane & 15, lk = lane >> 4;
+    int bi = blockIdx.x;
+    const int tn = bi % tiles_n;
+    bi /= tiles_n;
+    const int strip = bi % strips, b = bi / strips;
+    const int m_begin = strip * rows_per, m_end = min(s.Ho, m_begin + rows_per);
+    const int n0 = tn * CD_NT;
+    const int ci0 = 16 * wave;  // this wave's 16 input channels: their 64 x 9 weights stay in registers
+
+    float wr[9][16];
+#pragma unroll
+    for (int t = 0; t < 9; ++t)
+#pragma unroll
+        for (int ks = 0; ks < 16; ++ks) wr[t][ks] = w[((4 * ks + lk) * CW_C + ci0 + lc) * 9 + t];
+
+    const float* dyb = dy + (size_t)b * CW_C * s.Ho * s.Wo;
+    float* dxb = dx + ((size_t)b * CW_C + ci0 + 4 * lk) * s.H * s.W;
+    const float* brow = dys + lk * CD_CP + lc;
+    const bool pair_ok = (s.W & 1) == 0;  // rows of dX start 8-byte aligned
+    for (int m = m_begin; m < m_end; ++m) {
+        __syncthreads();  // the previous row pair's operand reads are done
+        for (int i = tid; i < CW_C * 2 * (CD_NT + 1); i += 256) {
+            const int co = i / (2 * (CD_NT + 1)), r = i - co * 2 * (CD_NT + 1), rr = r / (CD_NT + 1), c = r - rr * (CD_NT + 1);
+            const int oy = m + rr, ox = n0 + c;
+            dys[co * CD_CP + rr * CD_RP + c] = (oy < s.Ho && ox < s.Wo) ? dyb[((size_t)co * s.Ho + oy) * s.Wo + ox] : 0.f;
+        }
+        __syncthreads();
+#pragma unroll 1  // 144 MFMAs per group already: unrolling the groups only spills the weights
+        for (int ng = 0; ng < CD_NT / 16 && n0 + 16 * ng < s.Wo; ++ng) {
+            f32x4v acc[2][2];
+#pragma unroll
+            for (int i = 0; i < 2; ++i)
+#pragma unroll
+                for (int j = 0; j < 2; ++j) acc[i][j] = f32x4v{0.f, 0.f, 0.f, 0.f};
+            const float* bp = brow + 16 * ng;
+            // tap by tap, the 64 output channels of a tap as two interleaved chains of 32 (k-steps of 4 channels, even and odd:
+            // no MFMA waits on the one before it), folded into the class sum in a fixed order: the longest fp32 chain is 32
+            // terms, which keeps the result as close to fp64 as the stock kernel's
+#pragma unroll
+            for (int ky = 0; ky < 3; ++ky)
+#pragma unroll
+                for (int kx = 0; kx < 3; ++kx) {
+                    f32x4v p0 = {0.f, 0.f, 0.f, 0.f}, p1 = {0.f, 0.f, 0.f, 0.f};
+                    const float* bt = bp + cd_shift(ky) * CD_RP + cd_shift(kx);
+#pragma unroll
+                    for (int ks = 0; ks < 16; ks += 2) {
+                        p0 = mfma16(wr[3 * ky + kx][ks], bt[4 * ks * CD_CP], p0);
+                        p1 = mfma16(wr[3 * ky + kx][ks + 1], bt[4 * (ks + 1) * CD_CP], p1);
+                    }
+                    acc[cd_par(ky)][cd_par(kx)] += p0 + p1;
+                }
+            // column pair (2 n, 2 n + 1) of one lane: 16 lanes store 128 contiguous bytes of a dX row
+            const int ix = 2 * (n0 + 16 * ng + lc);
+#pragma unroll
+            for (int rp = 0; rp < 2; ++rp) {
+                const int iy = 2 * m + rp;
+                if (iy < s.H && ix < s.W) {
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) {
+                        float* p = dxb + ((size_t)r * s.H + iy) * s.W + ix;
+                        if (pair_ok) {
+                            *reinterpret_cast<f32x2*>(p) = f32x2{acc[rp][0][r], acc[rp][1][r]};
+                        } else {
+                            p[0] = acc[rp][0][r];
+                            if (ix + 1 < s.W) p[1] = acc[rp][1][r];
+                        }
+                    }
+                }
+            }
+        }
+    }
+}
+
+// ------------------------------------------------------------------------------------------------ host side
+bool conv3x3s2_supported(int Ci, int Co) { return (Ci == CW_C && Co == CW_C) || (Ci == CF_CI && Co == CF_CO); }
+
+static C3Plan cd_plan(const C3Shape& s) {  // strips of row pairs m per (image, 64-column tile), as cw_plan
+    C3Plan p;
+    p.tiles_x = ceil_div(s.Wo, CD_NT);
+    const long per = (long)s.B * p.tiles_x;
+    long strips = CW_TARGET_WG / per;
+    if (strips > s.Ho) strips = s.Ho;
+    if (strips < 1) strips = 1;
+    p.rows_per = ceil_div(s.Ho, (int)strips);
+    p.strips = ceil_div(s.Ho, p.rows_per);
+    return p;
+}
+
+long long conv3x3s2_dgrad_workgroups(int B, int H, int W) {
+    const C3Shape s = c3_shape(B, H, W);
+    const long long per = (long long)B * ceil_div(s.Wo, CD_NT);
+    if (per > (1ll << 30)) return per;
+    const C3Plan p = cd_plan(s);
+    return per * p.strips;
+}
+
+hipError_t conv3x3s2_dgrad_run(const float* dy, const float* w, int B, int H, int W, float* dx, hipStream_t stream) {
+    const C3Shape s = c3_shape(B, H, W);
+    const C3Plan p = cd_plan(s);
+    hipLaunchKernelGGL(conv3x3s2_dgrad64_kernel, dim3(B * p.tiles_x * p.strips), dim3(256), 0, stream, dy, w, s, p.tiles_x,
+                       p.strips, p.rows_per, dx);
+    return hipGetLastError();
+}
+
+// number of slabs (= workgroups) of the weight gradient, as a 64-bit count: the caller checks it against the grid limit
+long long conv3x3s2_wgrad_slabs(int B, int Ci, int H, int W) {
+    const C3Shape s = c3_shape(B, H, W);
+    if (Ci == CF_CI) return (long long)B * ceil_div(s.Ho, CF_TH);
+    const long long tiles_x = ceil_div(s.Wo, CW_TW);
+    if ((long long)B * tiles_x > (1ll << 30)) return (long long)B * tiles_x;
+    const C3Plan p = cw_plan(s);
+    return (long long)B * p.tiles_x * p.strips;
+}
+
+size_t conv3x3s2_wgrad_workspace(int B, int Ci, int H, int W) {
+    return align_up((size_t)conv3x3s2_wgrad_slabs(B, Ci, H, W) * (Ci == CF_CI ? CF_SLAB : CW_SLAB) * sizeof(float), 256);
+}
+
+hipError_t conv3x3s2_wgrad_run(const float* dy, const float* x, int B, int Ci, int H, int W, float* dw, void* ws,
+                               hipStream_t stream) {
+    const C3Shape s = c3_shape(B, H, W);
+    float* slabs = static_cast<float*>(ws);
+    const int nslab = (int)conv3x3s2_wgrad_slabs(B, Ci, H, W);
+    if (Ci == CF_CI) {
+        hipLaunchKernelGGL(conv3x3s2_wgrad_3_16_kernel, dim3(nslab), dim3(256), 0, stream, dy, x, s, ceil_div(s.Wo, CF_TW),
+                           slabs);
+    } else {
+        const C3Plan p = cw_plan(s);
+        const size_t lds = (size_t)(CW_C * CW_XP + CW_C * CW_DLD) * sizeof(float);
+        static lds_attr_mask mask{0};
+        if (hipError_t e = ensure_dynamic_lds(reinterpret_cast<const void*>(conv3x3s2_wgrad64_kernel), lds, mask); e != hipSuccess)
+            return e;
+        hipLaunchKernelGGL(conv3x3s2_wgrad64_kernel, dim3(nslab), dim3(256), lds, stream, dy, x, s, p.tiles_x, p.strips,
+                           p.rows_per, slabs);
+    }
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    slab_sum_launch(slabs, nslab, Ci == CF_CI ? CF_SLAB : CW_SLAB, dw, stream);
+    return hipGetLastError();
+}
+
+}  // namespace cabinet

@@ -19,6 +19,7 @@
 //   output  : the four partial tiles are added in wave order through the LDS (all threads), one slab per split; an ordered slab sum
 //             (no atomics) gives dW.  Bit-reproducible; no allocation, no host synchronisation.
 #include "common.hpp"
+#include "slab_sum.hpp"
 
 namespace cabinet {
 
@@ -126,36 +127,6 @@ __global__ __launch_bounds__(256, 2) void pww_wgrad_kernel(const float* __restri
         }
 }
 
-// dw[i] = sum over the slabs in a fixed order: 32 elements x Q slab lanes per workgroup (128-byte row segments; a lane adds
-// slabs q, q + Q, ... in four independent chains), then the Q partial sums in order.  Q = 32 where one tile was split
-// hundreds of ways (the thin layers: 512 slabs of 19 KB), Q = 8 for the few large slabs of the wide ones.
-template <int Q>
-__global__ __launch_bounds__(32 * Q) void pww_slab_sum_kernel(const float* __restrict__ slabs, int nslab, int count,
-                                                              float* __restrict__ dw) {
-    __shared__ float red[Q][32];
-    const int e = threadIdx.x & 31, q = threadIdx.x >> 5, i = blockIdx.x * 32 + e;
-    float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
-    if (i < count) {
-        const float* p = slabs + i;
-        int k = q;
-        for (; k + 3 * Q < nslab; k += 4 * Q) {
-            s0 += p[(size_t)k * count];
-            s1 += p[(size_t)(k + Q) * count];
-            s2 += p[(size_t)(k + 2 * Q) * count];
-            s3 += p[(size_t)(k + 3 * Q) * count];
-        }
-        for (; k < nslab; k += Q) s0 += p[(size_t)k * count];
-    }
-    red[q][e] = (s0 + s1) + (s2 + s3);
-    __syncthreads();
-    if (q == 0 && i < count) {
-        float t = red[0][e];
-#pragma unroll
-        for (int k = 1; k < Q; ++k) t += red[k][e];
-        dw[i] = t;
-    }
-}
-
 // ------------------------------------------------------------------------------------------------ host side
 struct PwwPlan {
     int bm, bn, tiles_m, tiles_n, nsplit, nchunks, cpi;
@@ -224,10 +195,7 @@ hipError_t pwconv_wide_wgrad_run(const float* dy, const float* x, int B, int Ci,
 #undef PWW
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
-    if (pl.nsplit >= 128)
-        hipLaunchKernelGGL(pww_slab_sum_kernel<32>, dim3(ceil_div(Co * Ci, 32)), dim3(1024), 0, stream, slabs, pl.nsplit, Co * Ci, dw);
-    else
-        hipLaunchKernelGGL(pww_slab_sum_kernel<8>, dim3(ceil_div(Co * Ci, 32)), dim3(256), 0, stream, slabs, pl.nsplit, Co * Ci, dw);
+    slab_sum_launch(slabs, pl.nsplit, Co * Ci, dw, stream);
     return hipGetLastError();
 }
 

@@ -14,8 +14,9 @@
 //   fwd : y[co][px]  = sum_k W[co][k] * patch[k][px]            A = W (LDS, stride 149), B = patch gather
 //   wrw : dW[co][k]  = sum_px dy[co][px] * patch[k][px]         A = dy tile (LDS, stride 129), B = patch gather,
 //         contraction over pixels; each wave accumulates the full 64 x 160 tile over its pixels, one ordered slab per
-//         workgroup, final ordered slab sum (no atomics).
+//         workgroup, final ordered slab sum (slab_sum.hpp; no atomics).
 #include "common.hpp"
+#include "slab_sum.hpp"
 
 namespace cabinet {
 
@@ -201,21 +202,6 @@ __global__ __launch_bounds__(256, 2) void stem_conv_wrw_kernel(const float* __re
     }
 }
 
-__global__ void stem_conv_wrw_reduce_kernel(const float* __restrict__ slabs, int nslab, float* __restrict__ dw) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= ST_CO * ST_KK) return;
-    float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
-    int k = 0;
-    for (; k + 3 < nslab; k += 4) {
-        s0 += slabs[(size_t)k * ST_CO * ST_KK + i];
-        s1 += slabs[(size_t)(k + 1) * ST_CO * ST_KK + i];
-        s2 += slabs[(size_t)(k + 2) * ST_CO * ST_KK + i];
-        s3 += slabs[(size_t)(k + 3) * ST_CO * ST_KK + i];
-    }
-    for (; k < nslab; ++k) s0 += slabs[(size_t)k * ST_CO * ST_KK + i];
-    dw[i] = (s0 + s1) + (s2 + s3);
-}
-
 static StemShape stem_shape(int B, int H, int W) {
     return StemShape{B, H, W, (H + 2 * ST_PAD - ST_K) / ST_S + 1, (W + 2 * ST_PAD - ST_K) / ST_S + 1};
 }
@@ -247,8 +233,10 @@ hipError_t stem_conv_wrw_run(const float* dy, const float* x, int B, int H, int 
     const size_t lds = ((size_t)ST_CO * SW_DLD + SW_PATCH) * sizeof(float);
     float* slabs = static_cast<float*>(ws);
     hipLaunchKernelGGL(stem_conv_wrw_kernel, dim3(nslab), dim3(256), lds, stream, dy, x, s, ceil_div(s.Wo, SW_TW), slabs);
-    hipLaunchKernelGGL(stem_conv_wrw_reduce_kernel, dim3(ceil_div(ST_CO * ST_KK, 256)), dim3(256), 0, stream, slabs, nslab,
-                       dw);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    // the slabs (1024 x 38 KB at 8 x 1024^2) summed on the whole chip: 32 slab lanes per 128-byte segment, then in order
+    slab_sum_launch(slabs, nslab, ST_CO * ST_KK, dw, stream);
     return hipGetLastError();
 }
 

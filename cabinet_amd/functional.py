@@ -1688,6 +1688,89 @@ def pwconv_wide(x, conv):
     return _PwConvWide.apply(x, conv.weight)
 
 
+# --------------------------------------------------------------------------- 3x3 stride-2 convolution: weight gradient (K15)
+
+
+# CABINET_CONV3X3S2=0: the 3x3 stride-2 convolutions go back to the stock operator entirely (MIOpen input gradient, MIOpen
+# weight gradient with its NCHW <-> NHWC copies for the first layer too) -- same-box A/B timing only
+CONV3X3S2_ENABLED = _os.environ.get("CABINET_CONV3X3S2", "1") != "0"
+
+
+def conv3x3s2_supported(conv, x):
+    """True for the bias-free 3x3 stride-2 padding-1 convolutions whose BACKWARD K15 computes straight on NCHW (the spatial
+    branch's conv2 / conv3, reference cabinet.py:112-113, and the backbone's first layer, mobilenetv3.py:173) -- in a forward
+    that records a graph for autograd only; fp32 device tensors outside autocast.  The forward stays the stock operator's."""
+    if not (CONV3X3S2_ENABLED and isinstance(conv, torch.nn.Conv2d) and x.is_cuda and x.dim() == 4):
+        return False
+    if not (conv.kernel_size == (3, 3) and conv.stride == (2, 2) and conv.padding == (1, 1) and conv.groups == 1
+            and conv.bias is None and conv.dilation == (1, 1) and conv.padding_mode == "zeros"):
+        return False
+    if not (torch.is_grad_enabled() and conv.weight.requires_grad) or torch.is_autocast_enabled():
+        return False
+    if x.dtype != torch.float32 or conv.weight.dtype != torch.float32 or x.shape[0] < 1 or x.shape[2] * x.shape[3] < 1:
+        return False
+    return x.shape[1] == conv.in_channels and bool(_lib.load().cabinet_conv3x3s2_supported(conv.in_channels, conv.out_channels))
+
+
+def _conv3x3s2_native_wgrad(Ci, B, H):
+    """Where cabinet_conv3x3s2_wgrad is routed, by measurement on MI355X (tools/time_conv3x3s2.py, profiles/conv3x3s2_summary.md):
+    the 3 -> 16 form where its one workgroup per four output rows fills the chip (>= 1024 of them: x1.5 at config 3; with the 512
+    of config 5 it only draws level with the stock call).  The 64 -> 64 form is 0.5-0.6x the stock call, layout copies included, and
+    is not routed."""
+    return Ci == 3 and B * (((H - 1) // 2 + 1 + 3) // 4) >= 1024
+
+
+class _Conv3x3S2(torch.autograd.Function):
+    """y = conv2d(x, weight, stride 2, padding 1) with the stock forward; dx of the 64 -> 64 layers by cabinet_conv3x3s2_dgrad
+    (the 3 -> 16 layer reads the image and has none), dw by cabinet_conv3x3s2_wgrad where _conv3x3s2_native_wgrad says so,
+    else by the stock operator."""
+
+    @staticmethod
+    def forward(fn_ctx, x, weight):
+        y = F.conv2d(x, weight, None, 2, 1)
+        fn_ctx.save_for_backward(x, weight)
+        return y
+
+    @staticmethod
+    def backward(fn_ctx, g):
+        x, w = fn_ctx.saved_tensors
+        lib = _lib.load()
+        xc, gc = _f32c(x), _f32c(g)
+        Co, Ci = w.shape[0], w.shape[1]
+        B, H, W = xc.shape[0], xc.shape[2], xc.shape[3]
+        cb = torch.ops.aten.convolution_backward
+        dx = None
+        if fn_ctx.needs_input_grad[0] and Ci == 64:
+            dx = torch.empty_like(xc)
+            with torch.cuda.device(x.device):
+                rc = lib.cabinet_conv3x3s2_dgrad(_ptr(gc), _ptr(_f32c(w)), B, Ci, Co, H, W, _ptr(dx), _stream_handle(x.device))
+            _lib.check(rc, "cabinet_conv3x3s2_dgrad")
+        elif fn_ctx.needs_input_grad[0]:
+            dx = cb(g, x, w, None, [2, 2], [1, 1], [1, 1], False, [0, 0], 1, [True, False, False])[0]
+        dw = None
+        if fn_ctx.needs_input_grad[1] and _conv3x3s2_native_wgrad(Ci, B, H):
+            dw = torch.empty((Co, Ci, 3, 3), dtype=torch.float32, device=x.device)
+            ws, nbytes = _workspace(lib.cabinet_conv3x3s2_wgrad_workspace_bytes(B, Ci, Co, H, W), x.device)
+            with torch.cuda.device(x.device):
+                rc = lib.cabinet_conv3x3s2_wgrad(_ptr(gc), _ptr(xc), B, Ci, Co, H, W, _ptr(dw), _ptr(ws), nbytes,
+                                                 _stream_handle(x.device))
+            _lib.check(rc, "cabinet_conv3x3s2_wgrad")
+        elif fn_ctx.needs_input_grad[1]:
+            dw = cb(g, x, w, None, [2, 2], [1, 1], [1, 1], False, [0, 0], 1, [False, True, False])[1]
+        return dx, dw
+
+
+class Conv2dS2(torch.nn.Conv2d):
+    """``nn.Conv2d`` (same parameters, same ``state_dict``) whose convolution is ``_Conv3x3S2`` where conv3x3s2_supported says
+    so and the stock operator everywhere else.  The route sits inside the module's own call, so forward hooks and pre-hooks
+    registered on the layer see it as they see any convolution.  The models build their stride-2 3x3 layers with it."""
+
+    def _conv_forward(self, input, weight, bias):
+        if bias is None and conv3x3s2_supported(self, input):
+            return _Conv3x3S2.apply(input, weight)
+        return super()._conv_forward(input, weight, bias)
+
+
 # --------------------------------------------------------------------------- evaluation tail (K13; no autograd)
 
 

@@ -26,7 +26,7 @@ import torch.nn.functional as F
 
 from .. import functional as _functional
 from ..functional import (batched_bn_counters, bn_act, bn_relu_cls, conv1x1, conv1x1_bias_supported, conv3x3, conv3x3_bn_part,
-                          conv3x3_supported, ffm_fused, ffm_fused_upsampled, pwconv_wide, pwconv_wide_supported, stem_conv,
+                          conv3x3_supported, Conv2dS2, ffm_fused, ffm_fused_upsampled, pwconv_wide, pwconv_wide_supported, stem_conv,
                           stem_conv_supported)
 from .cab import ContextAggregationBlock
 from .constants import MODEL_CONFIG, MOBILENETV3_CFGS
@@ -57,7 +57,7 @@ def _conv3x3_bn_relu(conv: nn.Conv2d, bn: nn.BatchNorm2d, x: torch.Tensor, x1: O
     xin = x if x1 is None else torch.cat([x, x1], dim=1)
     if pwconv_wide_supported(conv, xin):  # the spatial branch's 1x1 conv_out in training: NCHW weight gradient (K14)
         return bn_act(pwconv_wide(xin, conv), bn, "relu")
-    return bn_act(conv(xin), bn, "relu")
+    return bn_act(conv(xin), bn, "relu")  # stock; the spatial branch's 3x3/2 conv2 / conv3 are Conv2dS2: native backward (K15)
 
 
 def _conv3x3_bn_relu_cls(conv: nn.Conv2d, bn: nn.BatchNorm2d, cls: nn.Conv2d, x: torch.Tensor,
@@ -78,7 +78,8 @@ class ConvBNReLU(nn.Module):
     def __init__(self, in_chan: int, out_chan: int, kernel_size: int = 3, stride: int = 1, padding: int = 1,
                  dilation: int = 1):
         super().__init__()
-        self.conv = nn.Conv2d(in_chan, out_chan, kernel_size, stride, padding, dilation=dilation, bias=False)
+        # Conv2dS2: nn.Conv2d whose 3x3 stride-2 form (conv2, conv3) takes its backward from K15 in training
+        self.conv = Conv2dS2(in_chan, out_chan, kernel_size, stride, padding, dilation=dilation, bias=False)
         self.bn = nn.BatchNorm2d(out_chan)
         self.relu = nn.ReLU(inplace=True)
         self.init_weight()

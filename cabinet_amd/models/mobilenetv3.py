@@ -121,12 +121,14 @@ class _FusedSequential(nn.Sequential):
             elif pwconv_wide_supported(m, x):
                 x, i = pwconv_wide(x, m), i + 1  # wide 1x1 conv, training: stock forward / dx, NCHW weight gradient (K14)
             else:
-                x, i = m(x), i + 1
+                x, i = m(x), i + 1  # stock; the 3 -> 16 3x3/2 first layer is a Conv2dS2: native weight gradient (K15)
         return x if residual is None else residual + x
 
 
 def conv_3x3_bn(inp, oup, stride):
-    return _FusedSequential(nn.Conv2d(inp, oup, 3, stride, 1, bias=False), nn.BatchNorm2d(oup), HardSwish())
+    from ..functional import Conv2dS2  # nn.Conv2d whose stride-2 form takes its weight gradient from K15 in training
+
+    return _FusedSequential(Conv2dS2(inp, oup, 3, stride, 1, bias=False), nn.BatchNorm2d(oup), HardSwish())
 
 
 def conv_1x1_bn(inp, oup):

@@ -16,6 +16,7 @@ Python never travels to the GPU box), so the step recipe is restated:
 from __future__ import annotations
 
 import contextlib
+import gc
 import os
 
 import torch
@@ -34,6 +35,9 @@ _CAPTURE_MODE = "thread_local"
 def build_model(mode="large", n_classes=8, device="cpu", seed=0, gamma=None, freeze_unused=True):
     """Random-init CABiNet (model seed as in BASELINE.md); ``gamma`` overrides CAB's zero-init scale so
     the attention kernels influence logits and gradients (parity trap 1)."""
+    # a model dropped while it sits in reference cycles (patched forwards, hooks that close over it) keeps its tensors, device
+    # memory included, until the cyclic collector happens to run: collect now, not somewhere inside the next model's construction
+    gc.collect()
     torch.manual_seed(seed)
     net = CABiNet(n_classes=n_classes, cfgs=MOBILENETV3_CFGS[mode], mode=mode)
     if gamma is not None:

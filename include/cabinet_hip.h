@@ -606,6 +606,27 @@ int cabinet_eval_scale_merge(const float* prob, int N, int C, int FH, int FW, in
 int cabinet_eval_argmax_hist(const float* total, const long long* labels, int N, int C, int H, int W, int ignore_lb, long long* hist,
                              unsigned char* pred, cabinet_stream_t stream);
 
+/* ------------------------------------------------------------------------- *
+ * Weight and input gradient of the 3x3 stride-2 padding-1 bias-free convolutions (added under ABI v8): NCHW, no layout copy,
+ *   dw (Co,Ci,3,3) = sum_{b,oy,ox} dy (B,Co,Ho,Wo)[.,oy,ox] (x) x (B,Ci,H,W)[., 2 oy - 1 + ky, 2 ox - 1 + kx]
+ * with Ho = (H - 1) / 2 + 1, Wo = (W - 1) / 2 + 1.  Replaces the weight-gradient half of the autograd backward of
+ * ConvBNReLU(64, 64, kernel_size=3, stride=2, padding=1), src/models/cabinet.py:112-113 (SpatialBranch.conv2 / conv3,
+ * forward cabinet.py:42), and of conv_3x3_bn(3, input_channel, 2), src/models/mobilenetv3.py:173 (:86-91), the backbone's
+ * first layer.  Exact-fp32 MFMA with fp32 accumulation, one slab per workgroup, ordered slab sum: no atomics,
+ * bit-reproducible, capturable (the workspace comes from the caller).  The forward stays with the stock operator.
+ * Supported (cabinet_conv3x3s2_supported): (Ci, Co) = (64, 64) or (3, 16); any B, H, W >= 1.
+ *   dgrad (64 -> 64 only; the 3 -> 16 layer reads the image): w (Co,Ci,3,3),
+ *     dx (B,Ci,H,W)[., iy, ix] = sum_{co,ky,kx} w[co,.,ky,kx] * dy[., co, (iy + 1 - ky) / 2, (ix + 1 - kx) / 2]
+ *   over the taps with integer, in-range quotients, by the four parity classes of (iy, ix): no product with a structural
+ *   zero.  Every element of dx is written; no workspace, fixed summation order.
+ * ------------------------------------------------------------------------- */
+int cabinet_conv3x3s2_supported(int Ci, int Co);
+size_t cabinet_conv3x3s2_wgrad_workspace_bytes(int B, int Ci, int Co, int H, int W);
+int cabinet_conv3x3s2_wgrad(const float* dy, const float* x, int B, int Ci, int Co, int H, int W, float* dw,
+                            void* workspace, size_t workspace_bytes, cabinet_stream_t stream);
+int cabinet_conv3x3s2_dgrad(const float* dy, const float* w, int B, int Ci, int Co, int H, int W, float* dx,
+                            cabinet_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
