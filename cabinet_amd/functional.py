@@ -1655,6 +1655,7 @@ class _PwConvWide(torch.autograd.Function):
 
     @staticmethod
     def forward(fn_ctx, x, weight):
+        x = x.contiguous()  # dense NCHW for the stock operator too (a no-op in the model): a channels_last input sends it to another solver
         y = F.conv2d(x, weight)
         fn_ctx.save_for_backward(x, weight)
         return y
@@ -1662,6 +1663,7 @@ class _PwConvWide(torch.autograd.Function):
     @staticmethod
     def backward(fn_ctx, g):
         x, w = fn_ctx.saved_tensors
+        g = g.contiguous()
         dx = None
         if fn_ctx.needs_input_grad[0]:
             dx = torch.ops.aten.convolution_backward(g, x, w, None, [1, 1], [0, 0], [1, 1], False, [0, 0], 1,
@@ -1727,6 +1729,7 @@ class _Conv3x3S2(torch.autograd.Function):
 
     @staticmethod
     def forward(fn_ctx, x, weight):
+        x = x.contiguous()  # dense NCHW for the stock operator too (a no-op in the model): a channels_last input sends it to another solver
         y = F.conv2d(x, weight, None, 2, 1)
         fn_ctx.save_for_backward(x, weight)
         return y
@@ -1734,6 +1737,7 @@ class _Conv3x3S2(torch.autograd.Function):
     @staticmethod
     def backward(fn_ctx, g):
         x, w = fn_ctx.saved_tensors
+        g = g.contiguous()
         lib = _lib.load()
         xc, gc = _f32c(x), _f32c(g)
         Co, Ci = w.shape[0], w.shape[1]
