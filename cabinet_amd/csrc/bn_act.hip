@@ -45,6 +45,20 @@ __device__ __forceinline__ int ba_load(const float* __restrict__ row, int P, int
 __device__ __forceinline__ bool ba_valid(int P, int lo, int i, int e) {
     return lo + (i * BA_T + (int)threadIdx.x) * 4 + e < min(lo + BA_CHUNK, P);
 }
+// The chunk load of the element-wise kernels that merge statistics in their prologue (apply, dx).  AL (P % 4 == 0): no branch
+// around a load -- one past the end of the chunk reads the plane's last four elements instead, and what is computed from them is
+// never stored (ba_store).  Behind a branch per load the compiler waits for everything requested earlier (the prologue's
+// partials) before the first load and drains each block of loads before the next, and the merge could not run underneath them.
+template <bool AL>
+__device__ __forceinline__ void ba_request(const float* __restrict__ row, int P, int lo, f32x4 (&v)[BA_V]) {
+    if (AL) {
+#pragma unroll
+        for (int i = 0; i < BA_V; ++i)
+            v[i] = *reinterpret_cast<const f32x4*>(row + min(lo + (i * BA_T + (int)threadIdx.x) * 4, P - 4));
+    } else {
+        ba_load(row, P, lo, v);
+    }
+}
 __device__ __forceinline__ void ba_store(float* __restrict__ row, int P, int lo, const f32x4 (&v)[BA_V]) {
     const int hi = min(lo + BA_CHUNK, P);
     if ((P & 3) == 0) {
@@ -96,27 +110,33 @@ __global__ __launch_bounds__(BA_T) void bn_act_finalize_kernel(const float* __re
                                                                 float* __restrict__ running_var,
                                                                 float* __restrict__ save_mean,
                                                                 float* __restrict__ save_invstd) {
+    const BnPart first = bn_part_first(part, blockIdx.x, C, training ? bn_fwd_nt(B, chunks, conv_h, conv_w) : 0);
     bn_finalize_channel(part, blockIdx.x, B, C, P, chunks, conv_h, conv_w, training, momentum, eps, running_mean, running_var, save_mean,
-                        save_invstd);
+                        save_invstd, first, true);
 }
 
-__global__ __launch_bounds__(BA_T) void bn_act_apply_kernel(const float* __restrict__ x, const float* __restrict__ mean,
-                                                             const float* __restrict__ invstd,
+// m.on: the finalize runs here (BnFwdMerge, bn_finalize.hpp), underneath the workgroup's own activation loads; the writer is the
+// workgroup of image 0, chunk 0 of the channel
+template <bool AL>   // AL: P % 4 == 0, the host's choice
+__global__ __launch_bounds__(BA_T) void bn_act_apply_kernel(const float* __restrict__ x,
                                                              const float* __restrict__ weight,
                                                              const float* __restrict__ bias,
                                                              const float* __restrict__ residual, int C, int P,
-                                                             int chunks, int act, float* __restrict__ y) {
+                                                             int chunks, int act, float* __restrict__ y, BnFwdMerge m) {
     const int row = blockIdx.x / chunks, ch = blockIdx.x - row * chunks, c = row % C;
-    const float mu = mean[c], inv = invstd[c], gam = weight[c], bet = bias[c];
-    f32x4 v[BA_V];
-    ba_load(x + (size_t)row * P, P, ch * BA_CHUNK, v);
+    const float gam = weight[c], bet = bias[c];
+    BnPart first = bn_part_first(m, c, C, chunks);
+    f32x4 v[BA_V], r[BA_V];
+    ba_request<AL>(x + (size_t)row * P, P, ch * BA_CHUNK, v);
+    if (residual) ba_request<AL>(residual + (size_t)row * P, P, ch * BA_CHUNK, r);
+    bn_part_pin(first);
+    const BnStat st = bn_consumer_stat(m, c, C, P, chunks, first, row < C && ch == 0);
+    const float mu = st.mean, inv = st.invstd;
 #pragma unroll
     for (int i = 0; i < BA_V; ++i)
 #pragma unroll
         for (int e = 0; e < 4; ++e) v[i][e] = act_fwd(fmaf((v[i][e] - mu) * inv, gam, bet), act);
     if (residual) {  // the identity shortcut of an MBConv block (mobilenetv3.py:158), added in the same pass
-        f32x4 r[BA_V];
-        ba_load(residual + (size_t)row * P, P, ch * BA_CHUNK, r);
 #pragma unroll
         for (int i = 0; i < BA_V; ++i) v[i] += r[i];
     }
@@ -155,16 +175,23 @@ __global__ __launch_bounds__(BA_T) void bn_act_bwd_reduce_kernel(const float* __
 }
 
 // per channel: dbias = sum du, dweight = sum du*xhat, coef = (mean(du), mean(du*xhat)) (zeros in eval mode)
-__global__ __launch_bounds__(BA_T) void bn_act_bwd_finalize_kernel(const float* __restrict__ part, int nt, int C,
-                                                                    double count, int training,
-                                                                    float* __restrict__ dweight,
-                                                                    float* __restrict__ dbias, float* __restrict__ coef) {
+// (call from all BA_T threads of the block; every thread gets the coefficients, thread 0 of a `writer` block stores dweight /
+// dbias -- like bn_finalize_channel, one block's result depends on `part` and the fixed order only)
+struct BnCoef {
+    float m1, m2;
+};
+__device__ __forceinline__ BnCoef bn_bwd_finalize_channel(const float* __restrict__ part, int nt, int c, int C, double count,
+                                                          int training, float* __restrict__ dweight, float* __restrict__ dbias,
+                                                          BnPart first, bool writer) {
     __shared__ double dred[2][4];
-    const int c = blockIdx.x;
     double s1 = 0.0, s2 = 0.0;
-    for (int t = threadIdx.x; t < nt; t += BA_T) {
-        s1 += (double)part[(size_t)c * nt + t];
-        s2 += (double)part[((size_t)C + c) * nt + t];
+    if ((int)threadIdx.x < nt) {   // `first` = bn_part_first(part, c, C, nt)
+        s1 += (double)first.a;
+        s2 += (double)first.b;
+        for (int t = threadIdx.x + BA_T; t < nt; t += BA_T) {
+            s1 += (double)part[(size_t)c * nt + t];
+            s2 += (double)part[((size_t)C + c) * nt + t];
+        }
     }
 #pragma unroll
     for (int o = 32; o >= 1; o >>= 1) {
@@ -173,29 +200,57 @@ __global__ __launch_bounds__(BA_T) void bn_act_bwd_finalize_kernel(const float* 
     }
     if ((threadIdx.x & 63) == 0) dred[0][threadIdx.x >> 6] = s1, dred[1][threadIdx.x >> 6] = s2;
     __syncthreads();
-    if (threadIdx.x == 0) {
-        s1 = (dred[0][0] + dred[0][1]) + (dred[0][2] + dred[0][3]);
-        s2 = (dred[1][0] + dred[1][1]) + (dred[1][2] + dred[1][3]);
+    s1 = (dred[0][0] + dred[0][1]) + (dred[0][2] + dred[0][3]);
+    s2 = (dred[1][0] + dred[1][1]) + (dred[1][2] + dred[1][3]);
+    if (writer && threadIdx.x == 0) {
         dbias[c] = (float)s1;
         dweight[c] = (float)s2;
-        coef[c] = training ? (float)(s1 / count) : 0.f;
-        coef[C + c] = training ? (float)(s2 / count) : 0.f;
     }
+    return BnCoef{training ? (float)(s1 / count) : 0.f, training ? (float)(s2 / count) : 0.f};
 }
 
+__global__ __launch_bounds__(BA_T) void bn_act_bwd_finalize_kernel(const float* __restrict__ part, int nt, int C,
+                                                                    double count, int training,
+                                                                    float* __restrict__ dweight,
+                                                                    float* __restrict__ dbias, float* __restrict__ coef) {
+    const int c = blockIdx.x;
+    const BnCoef k = bn_bwd_finalize_channel(part, nt, c, C, count, training, dweight, dbias, bn_part_first(part, c, C, nt), true);
+    if (threadIdx.x == 0) coef[c] = k.m1, coef[C + c] = k.m2;
+}
+
+// the backward finalize as the dx pass's prologue (see BnFwdMerge, bn_finalize.hpp): the writer of dweight / dbias is the workgroup of image 0,
+// chunk 0 of the channel; `coef` is not used
+struct BnBwdMerge {
+    int on;             // 0: coef holds finished values (the stand-alone finalize ran in front)
+    const float* part;  // [2][C][nt] (sum du, sum du * xhat) partials
+    int nt, training;
+    double count;
+    float *dweight, *dbias;
+};
+
+template <bool AL>   // AL: P % 4 == 0, the host's choice
 __global__ __launch_bounds__(BA_T) void bn_act_bwd_dx_kernel(const float* __restrict__ dy, const float* __restrict__ x,
                                                               const float* __restrict__ mean,
                                                               const float* __restrict__ invstd,
                                                               const float* __restrict__ weight,
                                                               const float* __restrict__ bias,
                                                               const float* __restrict__ coef, int C, int P, int chunks,
-                                                              int act, float* __restrict__ dx) {
+                                                              int act, float* __restrict__ dx, BnBwdMerge m) {
     const int row = blockIdx.x / chunks, ch = blockIdx.x - row * chunks, c = row % C;
-    const float mu = mean[c], inv = invstd[c], gam = weight[c], bet = bias[c];
-    const float m1 = coef[c], m2 = coef[C + c], gi = gam * inv;
+    const float mu = mean[c], inv = invstd[c], gam = weight[c], bet = bias[c], gi = gam * inv;
+    BnPart first = bn_part_first(m.part, c, C, m.on ? m.nt : 0);
     f32x4 vx[BA_V], vg[BA_V];
-    ba_load(x + (size_t)row * P, P, ch * BA_CHUNK, vx);
-    ba_load(dy + (size_t)row * P, P, ch * BA_CHUNK, vg);
+    ba_request<AL>(x + (size_t)row * P, P, ch * BA_CHUNK, vx);
+    ba_request<AL>(dy + (size_t)row * P, P, ch * BA_CHUNK, vg);
+    bn_part_pin(first);
+    float m1, m2;
+    if (m.on) {
+        const BnCoef k = bn_bwd_finalize_channel(m.part, m.nt, c, C, m.count, m.training, m.dweight, m.dbias, first,
+                                                 row < C && ch == 0);
+        m1 = k.m1, m2 = k.m2;
+    } else {
+        m1 = coef[c], m2 = coef[C + c];
+    }
 #pragma unroll
     for (int i = 0; i < BA_V; ++i)
 #pragma unroll
@@ -206,6 +261,7 @@ __global__ __launch_bounds__(BA_T) void bn_act_bwd_dx_kernel(const float* __rest
         }
     ba_store(dx + (size_t)row * P, P, ch * BA_CHUNK, vg);
 }
+
 
 // ---- channel gate + activation (squeeze-excite tail, reference mobilenetv3.py:79-83 followed by :121/:141) ----
 // y = act(x * gate[b,c]);  backward: du = dy * act'(x*gate), dx = du * gate, dgate[b,c] = sum_p du * x
@@ -362,6 +418,25 @@ __global__ __launch_bounds__(BA_T) void se_bwd_dx_kernel(const float* __restrict
 
 static int ba_chunks(int P) { return ceil_div(P, BA_CHUNK); }
 
+// Launch plan of the two finalizes: merged in the consumer's prologue when a channel has at most BA_PROLOGUE_MAX_NT partials
+// (every consumer workgroup reads 2 nt floats of them: <= 8 KB against the 64-96 KB it streams), in the stand-alone kernel above
+// that (eval mode has no partials: nt = 0).  CABINET_BN_PROLOGUE=0 restores the stand-alone launch everywhere (read per call:
+// the tests flip it in-process).
+constexpr int BA_PROLOGUE_MAX_NT = 1024;
+static bool bn_prologue_plan(int nt) {
+    const char* e = getenv("CABINET_BN_PROLOGUE");
+    return !(e && e[0] == '0') && nt <= BA_PROLOGUE_MAX_NT;
+}
+static void apply_launch(int grid, hipStream_t stream, const float* x, const float* weight, const float* bias,
+                         const float* residual, int C, int P, int chunks, int act, float* y, const BnFwdMerge& m) {
+    if ((P & 3) == 0)
+        hipLaunchKernelGGL(bn_act_apply_kernel<true>, dim3(grid), dim3(BA_T), 0, stream, x, weight, bias, residual, C, P, chunks,
+                           act, y, m);
+    else
+        hipLaunchKernelGGL(bn_act_apply_kernel<false>, dim3(grid), dim3(BA_T), 0, stream, x, weight, bias, residual, C, P, chunks,
+                           act, y, m);
+}
+
 size_t se_act_bwd_workspace(int B, int C, int P) { return align_up((size_t)3 * B * C * ba_chunks(P) * sizeof(float), 256); }
 
 hipError_t se_act_bwd_reduce_run(const float* dy, const float* z, const float* mean, const float* invstd, const float* weight,
@@ -396,6 +471,23 @@ size_t bn_act_workspace(int B, int C, int P) {
     return align_up((size_t)2 * C * B * ba_chunks(P) * sizeof(float), 256) + align_up((size_t)2 * C * sizeof(float), 256);
 }
 
+// The statistics of x for the apply pass: with the finalize in its prologue (the returned m.on: the plan above) only the statistics
+// pass runs here, otherwise bn_stats_run.
+static BnFwdMerge bn_stats_merge_run(const float* x, float* running_mean, float* running_var, int B, int C, int P, int training,
+                              float momentum, float eps, float* save_mean, float* save_invstd, void* ws, hipStream_t stream) {
+    const int chunks = ba_chunks(P);
+    BnFwdMerge m{0, static_cast<const float*>(ws), B, 0, 0, training, momentum, eps, running_mean, running_var, save_mean, save_invstd};
+    if (bn_prologue_plan(training ? B * chunks : 0)) {
+        m.on = 1;
+        if (training)
+            hipLaunchKernelGGL(bn_act_stats_kernel, dim3(B * C * chunks), dim3(BA_T), 0, stream, x, static_cast<float*>(ws), B, C, P,
+                               chunks);
+    } else {
+        (void)bn_stats_run(x, running_mean, running_var, B, C, P, training, momentum, eps, save_mean, save_invstd, ws, stream);
+    }
+    return m;
+}
+
 hipError_t bn_stats_run(const float* x, float* running_mean, float* running_var, int B, int C, int P, int training,
                         float momentum, float eps, float* save_mean, float* save_invstd, void* ws, hipStream_t stream) {
     const int chunks = ba_chunks(P), grid = B * C * chunks;
@@ -412,10 +504,14 @@ hipError_t bn_act_fwd_part_run(const float* x, const float* conv_part, int H, in
                                float* running_mean, float* running_var, const float* residual, int B, int C, int act, int training,
                                float momentum, float eps, float* y, float* save_mean, float* save_invstd, hipStream_t stream) {
     const int P = H * W, chunks = ba_chunks(P), grid = B * C * chunks;
-    hipLaunchKernelGGL(bn_act_finalize_kernel, dim3(C), dim3(BA_T), 0, stream, conv_part, B, C, P, chunks, H, W, training, momentum,
-                       eps, running_mean, running_var, save_mean, save_invstd);
-    hipLaunchKernelGGL(bn_act_apply_kernel, dim3(grid), dim3(BA_T), 0, stream, x, save_mean, save_invstd, weight, bias,
-                       residual, C, P, chunks, act, y);
+    const int nt = B * ceil_div(H, 4) * ceil_div(W, 32);   // the producer's tile blocks (bn_finalize.hpp)
+    BnFwdMerge m{0, conv_part, B, H, W, training, momentum, eps, running_mean, running_var, save_mean, save_invstd};
+    if (bn_prologue_plan(training ? nt : 0))
+        m.on = 1;
+    else
+        hipLaunchKernelGGL(bn_act_finalize_kernel, dim3(C), dim3(BA_T), 0, stream, conv_part, B, C, P, chunks, H, W, training,
+                           momentum, eps, running_mean, running_var, save_mean, save_invstd);
+    apply_launch(grid, stream, x, weight, bias, residual, C, P, chunks, act, y, m);
     return hipGetLastError();
 }
 
@@ -424,9 +520,9 @@ hipError_t bn_act_fwd_run(const float* x, const float* weight, const float* bias
                           float momentum, float eps, float* y, float* save_mean, float* save_invstd, void* ws,
                           hipStream_t stream) {
     const int chunks = ba_chunks(P), grid = B * C * chunks;
-    (void)bn_stats_run(x, running_mean, running_var, B, C, P, training, momentum, eps, save_mean, save_invstd, ws, stream);
-    hipLaunchKernelGGL(bn_act_apply_kernel, dim3(grid), dim3(BA_T), 0, stream, x, save_mean, save_invstd, weight, bias,
-                       residual, C, P, chunks, act, y);
+    const BnFwdMerge m = bn_stats_merge_run(x, running_mean, running_var, B, C, P, training, momentum, eps, save_mean, save_invstd,
+                                            ws, stream);
+    apply_launch(grid, stream, x, weight, bias, residual, C, P, chunks, act, y, m);
     return hipGetLastError();
 }
 
@@ -435,10 +531,18 @@ hipError_t bn_bwd_tail_run(const float* part, int nt, const float* dy, const flo
                            int act, int training, float* dx, float* dweight, float* dbias, float* coef,
                            hipStream_t stream) {
     const int chunks = ba_chunks(P), grid = B * C * chunks;
-    hipLaunchKernelGGL(bn_act_bwd_finalize_kernel, dim3(C), dim3(BA_T), 0, stream, part, nt, C, (double)B * (double)P,
-                       training, dweight, dbias, coef);
-    hipLaunchKernelGGL(bn_act_bwd_dx_kernel, dim3(grid), dim3(BA_T), 0, stream, dy, x, save_mean, save_invstd, weight,
-                       bias, coef, C, P, chunks, act, dx);
+    BnBwdMerge m{0, part, nt, training, (double)B * (double)P, dweight, dbias};
+    if (bn_prologue_plan(nt))
+        m.on = 1;
+    else
+        hipLaunchKernelGGL(bn_act_bwd_finalize_kernel, dim3(C), dim3(BA_T), 0, stream, part, nt, C, m.count, training, dweight,
+                           dbias, coef);
+    if ((P & 3) == 0)
+        hipLaunchKernelGGL(bn_act_bwd_dx_kernel<true>, dim3(grid), dim3(BA_T), 0, stream, dy, x, save_mean, save_invstd, weight,
+                           bias, coef, C, P, chunks, act, dx, m);
+    else
+        hipLaunchKernelGGL(bn_act_bwd_dx_kernel<false>, dim3(grid), dim3(BA_T), 0, stream, dy, x, save_mean, save_invstd, weight,
+                           bias, coef, C, P, chunks, act, dx, m);
     return hipGetLastError();
 }
 

@@ -43,7 +43,8 @@ __global__ __launch_bounds__(BA_T) void bn_cls_table_kernel(const float* __restr
                                                              const float* __restrict__ bn_w, const float* __restrict__ bn_b,
                                                              const float* __restrict__ w_cls, int K, int KT, float* __restrict__ tab) {
     const int c = blockIdx.x;
-    if (mode == 1) bn_finalize_channel(part, c, B, C, P, 0, conv_h, conv_w, training, momentum, eps, running_mean, running_var, save_mean, save_invstd);
+    if (mode == 1) bn_finalize_channel(part, c, B, C, P, 0, conv_h, conv_w, training, momentum, eps, running_mean, running_var, save_mean, save_invstd,
+                                       bn_part_first(part, c, C, training ? bn_fwd_nt(B, 0, conv_h, conv_w) : 0), true);
     float* row = tab + (size_t)c * (KT + BC_X);
     if ((int)threadIdx.x < KT) row[threadIdx.x] = (int)threadIdx.x < K ? w_cls[(size_t)threadIdx.x * C + c] : 0.f;
     if (threadIdx.x == 0) {   // the thread that wrote save_mean / save_invstd in mode 1
