@@ -121,6 +121,9 @@ SIGNATURES = {
     "cabinet_se_act_bwd_reduce": (_INT, [_PTR] * 8 + [_INT] * 4 + [_PTR] * 2 + [_PTR, _SZ, _PTR]),
     "cabinet_se_act_bwd_coef": (_INT, [_PTR] * 3 + [_INT] * 4 + [_PTR] * 4 + [_PTR]),
     "cabinet_se_act_bwd_dx": (_INT, [_PTR] * 9 + [_INT] * 4 + [_PTR] + [_PTR]),
+    "cabinet_sgd_tail_workspace_bytes": (_SZ, [_INT]),
+    "cabinet_sgd_tail_state_bytes": (_SZ, [_INT]),
+    "cabinet_sgd_tail_step": (_INT, [_PTR, _INT, _PTR, _INT, _PTR, _PTR, _SZ, _INT, _PTR, _SZ, _PTR]),
 }
 
 _lock = threading.Lock()

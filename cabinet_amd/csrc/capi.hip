@@ -174,6 +174,11 @@ hipError_t eval_scale_merge_run(const float* prob, int N, int C, int FH, int FW,
                                 int H, int W, hipStream_t stream);
 hipError_t eval_argmax_hist_run(const float* total, const long long* labels, int N, int C, int H, int W, int ignore_lb, long long* hist,
                                 unsigned char* pred, hipStream_t stream);
+// opt_tail.hip
+size_t sgd_tail_workspace(int n_chunks);
+size_t sgd_tail_state(int n_entries);
+hipError_t sgd_tail_run(const cabinet_sgd_tail_entry* entries, int n_entries, const cabinet_sgd_tail_chunk* chunks, int n_chunks,
+                        const cabinet_sgd_tail_config& cfg, void* state, void* ws, int max_grid, hipStream_t stream);
 }  // namespace cabinet
 
 static thread_local char g_err[512] = "";
@@ -1356,6 +1361,33 @@ int cabinet_eval_argmax_hist(const float* total, const long long* labels, int N,
     if (reinterpret_cast<uintptr_t>(pred) & 3) return fail(CABINET_ERR_INVALID_ARG, "eval_argmax_hist: pred must be 4-byte aligned");
     return hip_status(cabinet::eval_argmax_hist_run(total, labels, N, C, H, W, ignore_lb, hist, pred, static_cast<hipStream_t>(stream)),
                       "eval_argmax_hist launch");
+}
+
+// ------------------------------------------------------ optimizer tail (K16): clip + warm-up / poly SGD + EMA
+size_t cabinet_sgd_tail_workspace_bytes(int n_chunks) { return n_chunks > 0 ? cabinet::sgd_tail_workspace(n_chunks) : 0; }
+
+size_t cabinet_sgd_tail_state_bytes(int n_entries) { return n_entries > 0 ? cabinet::sgd_tail_state(n_entries) : 0; }
+
+int cabinet_sgd_tail_step(const cabinet_sgd_tail_entry* entries, int n_entries, const cabinet_sgd_tail_chunk* chunks, int n_chunks,
+                          const cabinet_sgd_tail_config* config, void* state, size_t state_bytes, int max_grid, void* workspace,
+                          size_t workspace_bytes, cabinet_stream_t stream) {
+    if (n_entries <= 0 || n_chunks <= 0)
+        return fail(CABINET_ERR_INVALID_ARG, "sgd_tail_step: non-positive count n_entries=%d n_chunks=%d", n_entries, n_chunks);
+    if (!entries || !chunks) return fail(CABINET_ERR_INVALID_ARG, "sgd_tail_step: null table");
+    if (!config || !state) return fail(CABINET_ERR_INVALID_ARG, "sgd_tail_step: null config or state block");
+    if (max_grid < 0) return fail(CABINET_ERR_INVALID_ARG, "sgd_tail_step: negative max_grid=%d", max_grid);
+    if (!(config->max_iter > (double)config->warmup_steps) || config->warmup_steps < 0 || !(config->ema_tau > 0.0))
+        return fail(CABINET_ERR_INVALID_ARG, "sgd_tail_step: needs max_iter > warmup_steps >= 0 and ema_tau > 0");
+    if ((reinterpret_cast<uintptr_t>(entries) | reinterpret_cast<uintptr_t>(chunks) | reinterpret_cast<uintptr_t>(state)) & 7)
+        return fail(CABINET_ERR_INVALID_ARG, "sgd_tail_step: tables and state block must be 8-byte aligned");
+    if (state_bytes < cabinet_sgd_tail_state_bytes(n_entries))
+        return fail(CABINET_ERR_WORKSPACE, "sgd_tail_step: state block %zu < %zu bytes", state_bytes, cabinet_sgd_tail_state_bytes(n_entries));
+    const size_t need = cabinet_sgd_tail_workspace_bytes(n_chunks);
+    if (!workspace || workspace_bytes < need)
+        return fail(CABINET_ERR_WORKSPACE, "sgd_tail_step: workspace %zu < %zu bytes", workspace_bytes, need);
+    return hip_status(cabinet::sgd_tail_run(entries, n_entries, chunks, n_chunks, *config, state, workspace, max_grid,
+                                            static_cast<hipStream_t>(stream)),
+                      "sgd_tail_step launch");
 }
 
 }  // extern "C"

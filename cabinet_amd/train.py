@@ -187,12 +187,15 @@ class _OptimizerSegment:
     for ever.  ``before`` (e.g. gradient clipping, train.py:411-427) runs between backward and the step.
     ``capture=True`` records the step into its own hipGraph for a plain torch optimizer with constant hyper-parameters;
     the param-group scalars are snapshotted at capture and a replay with changed values RAISES instead of silently
-    stepping with the old ones.  A wrapper object whose ``step`` does host-side work must not be captured."""
+    stepping with the old ones.  A wrapper object whose ``step`` does host-side work must not be captured; an object that
+    declares ``capturable = True`` (``cabinet_amd.optim.FusedSGDTail``: schedule, step counter, clipping and EMA on the device)
+    is recorded as it is, after its ``prepare_capture()`` has brought its address table up to date outside the capture."""
 
     def __init__(self, optimizer, capture=False, before=None):
         self.optimizer, self.capture, self.before = optimizer, bool(capture), before
         self.graph = self.snapshot = None
-        if self.capture and optimizer is not None and not isinstance(optimizer, torch.optim.Optimizer):
+        if self.capture and optimizer is not None and not isinstance(optimizer, torch.optim.Optimizer) \
+                and getattr(optimizer, "capturable", None) is not True:
             raise RuntimeError("capture_optimizer=True needs a plain torch.optim.Optimizer: a wrapper's Python-side "
                                "schedule (warm-up, decay, step counter) would be frozen at its capture-time values")
         if self.capture and optimizer is not None and before is not None:  # at construction, not `warmup` steps later
@@ -204,6 +207,8 @@ class _OptimizerSegment:
         if self.before is not None:
             raise RuntimeError("capture_optimizer=True cannot run a `before_optimizer` callback between the graphs")
         self.snapshot = _hyper_snapshot(self.optimizer)
+        if hasattr(self.optimizer, "prepare_capture"):
+            self.optimizer.prepare_capture()
         self.graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(self.graph, pool=pool, capture_error_mode=_CAPTURE_MODE):
             self.optimizer.step()
@@ -231,7 +236,8 @@ class GraphedTrainStep:
         graph A   forward of the network + the OHEM forward kernels of both heads + their reduced statistics
         host      reads the 2 x (n_valid, n_above) counts and decides the OHEM branch      (the step's one sync)
         graph B   OHEM 'at least n_min pixels above thresh' branch, loss, backward
-        eager     optimizer.step() (see _OptimizerSegment: schedules and clipping are host-side; opt-in graph for constant lr)
+        eager     optimizer.step() (see _OptimizerSegment: schedules and clipping are host-side; opt-in graph for constant lr,
+                  or for cabinet_amd.optim.FusedSGDTail, whose schedule, clipping and EMA run on the device)
 
     and replayed with three host calls.  Nothing data-dependent is baked into a kernel argument (n_above is a device
     scalar in the loss).  If the host read says a head needs the rare top-n_min branch (or has no valid pixel), the step

@@ -627,6 +627,95 @@ int cabinet_conv3x3s2_wgrad(const float* dy, const float* x, int B, int Ci, int 
 int cabinet_conv3x3s2_dgrad(const float* dy, const float* w, int B, int Ci, int Co, int H, int W, float* dx,
                             cabinet_stream_t stream);
 
+/* ------------------------------------------------------------------------- *
+ * Optimizer tail (K16): gradient clipping, warm-up / poly SGD with momentum and
+ * per-group weight decay, and the weight EMA, as three launches on `stream`.
+ * Replaces src/scripts/train.py:411-427 per step:
+ *     clip_grad_norm_(net.parameters(), max_grad_norm)
+ *     optim.step()        (src/utils/optimizer.py:124-156: host-side schedule + torch SGD)
+ *     ema.update(net)     (src/utils/ema.py:51-62: two launches per state_dict entry)
+ * ADDITIVE to ABI version 8: no existing entry point, constant or layout changes, so a
+ * caller built against the earlier v8 header is unaffected and the version stays 8.
+ *
+ * The step counter `it`, the EMA counter `updates` and the schedule live in DEVICE
+ * memory (the state block), so a hipGraph replay of the call advances them.
+ *
+ * Tables (device memory, built by the caller once; NOT kernel arguments, any count):
+ *   entries[n_entries]  one per floating-point tensor.  param/grad/buf/ema are dense
+ *                       fp32 arrays of `numel` elements in the SAME element order.
+ *                       flags & CABINET_SGD_TAIL_EMA_ONLY (or grad == NULL): only
+ *                       ema = d*ema + (1-d)*param runs (BatchNorm running statistics,
+ *                       frozen parameters, parameters without a gradient this step).
+ *                       buf may be NULL when momentum == 0, ema NULL without an EMA.
+ *                       group: index 0..3 into the config's per-group arrays.
+ *   chunks[n_chunks]    (tensor, start, length): length <= CABINET_SGD_TAIL_CHUNK and
+ *                       start a multiple of it, so that a chunk is as aligned as its
+ *                       tensor; every element of every entry in exactly one chunk.
+ *                       A chunk that leaves its tensor or names no entry is ignored.
+ * Pointers need 4-byte alignment only: chunks whose pointers are 16-byte aligned move
+ * as float4, the others (and each chunk's last numel % 4 elements) as scalars.
+ *
+ * State block, cabinet_sgd_tail_state_bytes(n_entries) bytes of device memory, zeroed by
+ * the caller before the first step (byte offsets; all fields may be read or preset by
+ * the caller between steps, e.g. to resume):
+ *     0 int64 it        8 int64 updates      16 int64 skipped
+ *    24 int32 nonfinite (last step)          28 int32 apply (last step ran)
+ *    32 float last_grad_norm   36 float clip coefficient   40 float lr[4]
+ *    56 float d (EMA factor)   60 float 1-d
+ *   128 int32 valid[n_entries]  momentum buffer of entry i holds a value (0: the next
+ *       step sets buf = g, torch's first-step rule); then int32 first[n_entries] (scratch)
+ * Workspace: cabinet_sgd_tail_workspace_bytes(n_chunks), one fp32 partial per chunk.
+ *
+ * Per step:  norm = sqrt(sum over owned entries of g^2) -- per-chunk fp32 partials in a
+ * fixed order, summed in double, no atomics: bit-reproducible;
+ *   coef = max_norm > 0 ? min(1, max_norm / (norm + 1e-6)) : 1;
+ *   lr_g = float(lr_scale[g] * (it < warmup ? start + it/warmup * (lr0 - start)
+ *                                           : lr0 * (1 - k)^power)),
+ *          k = clamp((it - warmup) / (max_iter - warmup), 0, 1), in double
+ *          (past max_iter the reference's formula leaves the reals; here lr = 0);
+ *   updates += 1; d = decay * (1 - exp(-updates / tau)); it += 1;
+ *   per element: g = g*coef; if wd_g != 0: g += wd_g*p; buf = valid ? momentum*buf + g : g;
+ *                p -= lr_g*buf; ema = d*ema + (1-d)*p.
+ * With skip_nonfinite != 0 and a norm that is inf or nan NOTHING is written but
+ * last_grad_norm / nonfinite / apply, the counters do not advance and `skipped` goes up
+ * by one (what scaler.step and the `optim.it != prev_it` gate do in train.py:419-427).
+ * max_grid: 0 = the default cap of 2048 workgroups; smaller values force the
+ * grid-stride loop (tests).
+ * ------------------------------------------------------------------------- */
+#define CABINET_SGD_TAIL_CHUNK 4096
+#define CABINET_SGD_TAIL_EMA_ONLY 1
+
+typedef struct cabinet_sgd_tail_entry {
+    float* param;
+    const float* grad;
+    float* buf;
+    float* ema;
+    long long numel;
+    int group;
+    int flags;
+} cabinet_sgd_tail_entry; /* 48 bytes */
+
+typedef struct cabinet_sgd_tail_chunk {
+    long long start;
+    int tensor;
+    int length;
+} cabinet_sgd_tail_chunk; /* 16 bytes */
+
+typedef struct cabinet_sgd_tail_config { /* host memory, read during the call */
+    double lr0, warmup_start_lr, max_iter, power;
+    double lr_scale[4], weight_decay[4];
+    double momentum, max_norm, ema_decay, ema_tau;
+    long long warmup_steps;
+    int skip_nonfinite;
+    int reserved;
+} cabinet_sgd_tail_config;
+
+size_t cabinet_sgd_tail_workspace_bytes(int n_chunks);
+size_t cabinet_sgd_tail_state_bytes(int n_entries);
+int cabinet_sgd_tail_step(const cabinet_sgd_tail_entry* entries, int n_entries, const cabinet_sgd_tail_chunk* chunks, int n_chunks,
+                          const cabinet_sgd_tail_config* config, void* state, size_t state_bytes, int max_grid,
+                          void* workspace, size_t workspace_bytes, cabinet_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
