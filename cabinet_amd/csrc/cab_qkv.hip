@@ -99,83 +99,7 @@ static void stage_weights(const TrJobs& jobs, int n, hipStream_t stream) {
 //   zq -> q = relu(bn(zq));   zk -> kk = relu(bn(zk)) and its pooled bins;   vv -> its pooled bins.
 // pooled is written block-expanded: row (i, c) holds the bins of size i of channel c and zeros elsewhere, so
 // that  T[m][bin] = sum_{(i,c)} W_p[m][Kc + i*Kc + c] * pooled[(i,c)][bin]  is a plain GEMM.
-__global__ __launch_bounds__(256) void qkv_plane_fwd_kernel(const float* __restrict__ zqk, const float* __restrict__ vv,
-                                                             const float* __restrict__ mean, const float* __restrict__ invstd,
-                                                             const float* __restrict__ bnq_w, const float* __restrict__ bnq_b,
-                                                             const float* __restrict__ bnk_w, const float* __restrict__ bnk_b,
-                                                             int Kc, int Vc, PyrGeom g, float* __restrict__ q,
-                                                             float* __restrict__ kk, float* __restrict__ pooled_k,
-                                                             float* __restrict__ pooled_v) {
-    extern __shared__ __attribute__((aligned(16))) float smem[];
-    const int P = g.H * g.W, Mtot = 2 * Kc + Vc;
-    const int b = blockIdx.x / Mtot, m = blockIdx.x - b * Mtot, tid = threadIdx.x;
-    const int WS = g.W + 1;            // padded row stride: column sums below walk rows in lock step (bank conflicts otherwise)
-    float* plane = smem;               // [H][WS]
-    float* rowpart = smem + g.H * WS;  // [H][NCB]
-    float* binv = rowpart + g.H * g.NCB;  // [NBp]
-    float* pooled;
-    int ch, nch;
-    if (m < 2 * Kc) {
-        const float* src = zqk + ((size_t)b * 2 * Kc + m) * P;
-        const bool is_q = m < Kc;
-        ch = is_q ? m : m - Kc;
-        const float gam = is_q ? bnq_w[ch] : bnk_w[ch], bet = is_q ? bnq_b[ch] : bnk_b[ch];
-        const float mu = mean[m], inv = invstd[m];
-        float* dst = (is_q ? q : kk) + ((size_t)b * Kc + ch) * P;
-        if (is_q) {
-            for (int p = tid; p < P; p += 256) dst[p] = fmaxf(fmaf((src[p] - mu) * inv, gam, bet), 0.f);
-            return;
-        }
-        for (int p = tid; p < P; p += 256) {
-            const float v = fmaxf(fmaf((src[p] - mu) * inv, gam, bet), 0.f);  // same expression as the backward mask
-            const int y = p / g.W;
-            dst[p] = v;
-            plane[y * WS + (p - y * g.W)] = v;
-        }
-        pooled = pooled_k, nch = Kc;
-    } else {
-        ch = m - 2 * Kc, nch = Vc, pooled = pooled_v;
-        const float* src = vv + ((size_t)b * Vc + ch) * P;
-        for (int p = tid; p < P; p += 256) {
-            const int y = p / g.W;
-            plane[y * WS + (p - y * g.W)] = src[p];
-        }
-    }
-    __syncthreads();
-    // separable adaptive average pooling: column bins per row, then row bins
-    for (int it = tid; it < g.H * g.NCB; it += 256) {
-        const int y = it / g.NCB, cb = it - y * g.NCB;
-        int i = 0;
-        while (i + 1 < g.ns && cb >= g.coff[i + 1]) ++i;
-        const int c = cb - g.coff[i], xs = bin_start(c, g.W, g.s[i]), xe = bin_end(c, g.W, g.s[i]);
-        float acc = 0.f;
-        for (int x = xs; x < xe; ++x) acc += plane[y * WS + x];
-        rowpart[it] = acc;
-    }
-    __syncthreads();
-    for (int t = tid; t < g.NBp; t += 256) {
-        float val = 0.f;
-        if (t < g.NB) {
-            int i = 0;
-            while (i + 1 < g.ns && t >= g.off[i + 1]) ++i;
-            const int s = g.s[i], r = (t - g.off[i]) / s, c = (t - g.off[i]) - r * s;
-            const int ys = bin_start(r, g.H, s), ye = bin_end(r, g.H, s);
-            const int xs = bin_start(c, g.W, s), xe = bin_end(c, g.W, s);
-            float acc = 0.f;
-            for (int y = ys; y < ye; ++y) acc += rowpart[y * g.NCB + g.coff[i] + c];
-            val = acc / (float)((ye - ys) * (xe - xs));
-        }
-        binv[t] = val;
-    }
-    __syncthreads();
-    for (int it = tid; it < g.ns * g.NBp; it += 256) {
-        const int i = it / g.NBp, t = it - i * g.NBp;
-        const bool mine = t >= g.off[i] && t < g.off[i] + g.s[i] * g.s[i];
-        pooled[(((size_t)b * g.ns + i) * nch + ch) * g.NBp + t] = mine ? binv[t] : 0.f;
-    }
-}
-
-// ---- round 5: the same pass with the BatchNorm finalize in its prologue -----------------------------------------------------------
+// Round 5 put the BatchNorm finalize in this pass's prologue:
 // With `part` (training): the (mean, M2) partials the projection GEMM's epilogue left per (channel, image, 64-column tile) are merged
 // here -- equal counts, fixed order, double -- by wave 0 of every workgroup of the channel (128 pairs at config 3: two per lane) while
 // the other waves' plane loads are in flight; the b == 0 workgroup writes save_mean / save_invstd and the running buffers: the
@@ -267,7 +191,7 @@ __global__ __launch_bounds__(256) void qkv_plane_fwd_w_kernel(PlaneWArgs a, PyrG
                 v = fmaxf(fmaf((v - mu) * inv, gam, bet), 0.f);  // same expression as the backward mask
                 dst[p] = v;
             }
-            const int y = idiv_small(p, inv_w);
+            const int y = idiv_small(p, inv_w);   // exact: a supported plane fits LDS, H (W + 1) <= 16384
             plane[y * WS + (p - y * g.W)] = v;
         };
 #pragma unroll
@@ -276,7 +200,7 @@ __global__ __launch_bounds__(256) void qkv_plane_fwd_w_kernel(PlaneWArgs a, PyrG
         for (int p = tid + 256 * PRE; p < P; p += 256) put(p, src[p]);
     }
     __syncthreads();
-    // separable adaptive average pooling: column bins per row, then row bins (the arithmetic of qkv_plane_fwd_kernel, same order)
+    // separable adaptive average pooling: column bins per row, then row bins
     for (int it = tid; it < g.H * g.NCB; it += 256) {
         const int y = it / g.NCB, cb = it - y * g.NCB;
         int i = 0;
@@ -806,9 +730,7 @@ hipError_t qkv_fwd_run(const QkvShape& s, const QkvParams& w, const float* x, in
     auto at = [&](size_t o) { return reinterpret_cast<float*>(base + o); };
     const bool fused = qkv_fused_fwd_supported(s);
     // round 5: BatchNorm statistics from the projection GEMM's epilogue, finalize in the plane pass's prologue (3 launches instead of
-    // 4 where the output stage is fused too); CABINET_QKV_STATS_FUSED=0 keeps the round-4 launches (A/B timing)
-    static const bool plane_wave_on = [] { const char* e = getenv("CABINET_QKV_STATS_FUSED"); return !(e && e[0] == '0'); }();
-    const bool wplane = plane_wave_on && P < (1 << 21);
+    // 4 where the output stage is fused too)
     const int tiles_p = ceil_div(P, SG_TILE_P);
     bool stats_in_gemm = false;
     {
@@ -817,29 +739,24 @@ hipError_t qkv_fwd_run(const QkvShape& s, const QkvParams& w, const float* x, in
         jobs.j[0] = sg_job(w.wq, s.C, 1, x, s.C, s.C, s.Kc, P, sv.zqk, 2 * s.Kc);
         jobs.j[1] = sg_job(w.wk, s.C, 1, x, s.C, s.C, s.Kc, P, sv.zqk + (size_t)s.Kc * P, 2 * s.Kc);
         jobs.j[2] = sg_job(w.wv, s.C, 1, x, s.C, s.C, s.Vc, P, sv.vv, s.Vc);
-        if (wplane && training) {
+        if (training) {
             jobs.j[0].stat = at(L.stat);
             jobs.j[1].stat = at(L.stat) + (size_t)s.Kc * s.B * tiles_p * 2;
         }
-        stats_in_gemm = sg_gemm(jobs, s.B, stream) && wplane && training;
+        stats_in_gemm = sg_gemm(jobs, s.B, stream) && training;
     }
     // (a channel-resident form of these two launches -- statistics + plane pass of one stacked channel over all B images in one
     // workgroup, as the backward uses -- measured 36 us against 5 + 19: 384 workgroups leave the pooling phases latency-bound)
     if (!stats_in_gemm)
         hipLaunchKernelGGL(qk_bn_stats_kernel, dim3(2 * s.Kc), dim3(QS_T), 0, stream, sv.zqk, s.B, s.Kc, P, training, momentum, eps,
                            w.bnq_rm, w.bnq_rv, w.bnk_rm, w.bnk_rv, sv.mean, sv.invstd);
-    if (wplane) {
-        PlaneWArgs pa{};
-        pa.zqk = sv.zqk, pa.vv = sv.vv, pa.part = stats_in_gemm ? at(L.stat) : nullptr, pa.npairs = s.B * tiles_p;
-        pa.momentum = momentum, pa.eps = eps;
-        pa.q_rm = w.bnq_rm, pa.q_rv = w.bnq_rv, pa.k_rm = w.bnk_rm, pa.k_rv = w.bnk_rv, pa.save_mean = sv.mean, pa.save_invstd = sv.invstd;
-        pa.bnq_w = w.bnq_w, pa.bnq_b = w.bnq_b, pa.bnk_w = w.bnk_w, pa.bnk_b = w.bnk_b;
-        pa.B = s.B, pa.Kc = s.Kc, pa.Vc = s.Vc, pa.q = q, pa.kk = sv.kk, pa.pooled_k = sv.pooled_k, pa.pooled_v = sv.pooled_v;
-        hipLaunchKernelGGL(qkv_plane_fwd_w_kernel, dim3(s.B * Mtot), dim3(256), lds_fwd_plane(g), stream, pa, g);
-    } else {
-        hipLaunchKernelGGL(qkv_plane_fwd_kernel, dim3(s.B * Mtot), dim3(256), lds_fwd_plane(g), stream, sv.zqk, sv.vv, sv.mean,
-                           sv.invstd, w.bnq_w, w.bnq_b, w.bnk_w, w.bnk_b, s.Kc, s.Vc, g, q, sv.kk, sv.pooled_k, sv.pooled_v);
-    }
+    PlaneWArgs pa{};
+    pa.zqk = sv.zqk, pa.vv = sv.vv, pa.part = stats_in_gemm ? at(L.stat) : nullptr, pa.npairs = s.B * tiles_p;
+    pa.momentum = momentum, pa.eps = eps;
+    pa.q_rm = w.bnq_rm, pa.q_rv = w.bnq_rv, pa.k_rm = w.bnk_rm, pa.k_rv = w.bnk_rv, pa.save_mean = sv.mean, pa.save_invstd = sv.invstd;
+    pa.bnq_w = w.bnq_w, pa.bnq_b = w.bnq_b, pa.bnk_w = w.bnk_w, pa.bnk_b = w.bnk_b;
+    pa.B = s.B, pa.Kc = s.Kc, pa.Vc = s.Vc, pa.q = q, pa.kk = sv.kk, pa.pooled_k = sv.pooled_k, pa.pooled_v = sv.pooled_v;
+    hipLaunchKernelGGL(qkv_plane_fwd_w_kernel, dim3(s.B * Mtot), dim3(256), lds_fwd_plane(g), stream, pa, g);
     if (fused) {  // the output products with the pyramid terms formed per workgroup (one launch instead of two)
         if (hipError_t e = qkv_fused_out(s, w, sv, k, v, stream); e != hipSuccess) return e;
         return hipGetLastError();

@@ -10,8 +10,9 @@
 //             M-major (a row-major (M,K) weight as PyTorch stores it: no staging/transposition kernel in front);
 //   sg_dw     dW[m][n] = sum_{b,p} A[b][m][p] X[b][n][p], 64x64 tiles, split over position ranges, up to 8 products per
 //             launch, ONE ordered slab-sum launch for all of them (deterministic, no atomics).
-// v_mfma_f32_32x32x2_f32 throughout (exact fp32).  Operands with the contracted index contiguous go through stride-33
-// LDS images (conflict-free column reads); the others are read row-wise from stride-68 chunks.
+// v_mfma_f32_32x32x2_f32 throughout (exact fp32).  sg_gemm has a generic kernel ([k][row] LDS chunks at stride 68, an operand
+// with the contracted index contiguous transposed on the way in) and a fast one for launches of full, aligned tiles; sg_dw and
+// the fast kernel keep an operand with the contracted index contiguous as a [row][32 k] image at pitch 36.
 #include "blocks.hpp"
 #include "common.hpp"
 
@@ -22,15 +23,14 @@ namespace cabinet {
 constexpr int SG_T = 64;     // output tile edge
 constexpr int SG_BK = 32;    // contraction chunk
 constexpr int SG_STR = 68;   // LDS row stride of a [k][64] chunk (16-byte aligned rows)
-constexpr int SD_STR = 33;   // LDS row stride of a [row][32 positions] image
 
 // MB: 64-row blocks of the output tile per workgroup (tile = 64*MB x 64).  MB = 2 halves the B-operand traffic of a
 // product whose B is the big operand (dq = dS K^T: dS is 33.5 MB and was read once per 64-row tile of the 128 channels).
-// FAST: every job of the launch has full tiles (M % (64 MB) == 0, P % 64 == 0), whole chunks (every K-segment % 32 == 0) and
-// 16-byte aligned rows.  Then the loader has no bounds logic, its per-thread offsets and the key-mean bias are computed once,
-// and the segment descriptor (kernarg scalar loads) is only touched when a K-segment ends.  The generic loader spent ~134
-// VALU + 94 SALU instructions and 7 dependent kernarg loads per 32-deep chunk (16 MFMAs): MFMA utilisation 34 %.
-template <int MB, bool FAST>
+// This is the generic kernel: partial tiles, K-segments of any length (% 4), rows off a 16-byte boundary and a position-major B
+// are all handled per chunk, with the segment found and every bound checked anew.  That loader spends ~134 VALU + 94 SALU
+// instructions and 7 dependent kernarg loads per 32-deep chunk (16 MFMAs): MFMA utilisation 34 %, which is why launches that
+// need none of it go to sg_gemm_fast_kernel below.  No statistics epilogue: a caller that wants `stat` checks sg_gemm's result.
+template <int MB>
 __global__ __launch_bounds__(256) void sg_gemm_kernel(const SgJobs jobs) {
     constexpr int MT = SG_T * MB, ASTR = MT + 4, ASTR_T = MT + 1;
     __shared__ __attribute__((aligned(16))) float As[2][SG_BK * ASTR];
@@ -58,44 +58,6 @@ __global__ __launch_bounds__(256) void sg_gemm_kernel(const SgJobs jobs) {
         for (int r = 0; r < 16; ++r) acc[mb][r] = 0.f;
 
     f32x4 ra[2 * MB], rb[2];
-    // ---- FAST loader state: per-thread element offsets (chunk 0 of the current segment), scalar segment cursors
-    int offA[2 * MB], offB[2];
-    float biasv[2 * MB];
-    const float* apc = nullptr;
-    const float* bpc = nullptr;
-    int seg_cur = 0, seg_left = 0;
-    const int stepA = J.a_mmajor ? SG_BK : SG_BK * lda, stepB = J.b_pmajor ? SG_BK : SG_BK * ldp;
-    auto open_segment = [&](int sgi) {
-        seg_cur = sgi, seg_left = J.nck[sgi];
-        apc = J.seg[sgi].a + (size_t)b * J.a_img_stride;
-        bpc = J.seg[sgi].b + (size_t)b * J.seg[sgi].b_rows * (J.b_pmajor ? J.ldb : ldp);
-    };
-    if (FAST) {
-#pragma unroll
-        for (int i = 0; i < 2 * MB; ++i) {
-            const int idx = tid + i * 256;
-            offA[i] = J.a_mmajor ? (m0 + (idx >> 3)) * lda + (idx & 7) * 4 : (idx / (MT / 4)) * lda + m0 + (idx % (MT / 4)) * 4;
-            biasv[i] = (J.a_mmajor && J.a_bias) ? J.a_bias[(size_t)b * M + m0 + (idx >> 3)] : 0.f;
-        }
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {
-            const int idx = tid + i * 256;
-            offB[i] = J.b_pmajor ? (p0 + (idx >> 3)) * J.ldb + (idx & 7) * 4 : (idx >> 4) * ldp + p0 + (idx & 15) * 4;
-        }
-        open_segment(0);
-    }
-    auto load_next = [&]() {  // FAST: the chunks are fetched strictly in order
-#pragma unroll
-        for (int i = 0; i < 2 * MB; ++i) {
-            ra[i] = *reinterpret_cast<const f32x4*>(apc + offA[i]);
-#pragma unroll
-            for (int e = 0; e < 4; ++e) ra[i][e] -= biasv[i];
-        }
-#pragma unroll
-        for (int i = 0; i < 2; ++i) rb[i] = *reinterpret_cast<const f32x4*>(bpc + offB[i]);
-        apc += stepA, bpc += stepB;
-        if (--seg_left == 0 && seg_cur + 1 < J.nseg) open_segment(seg_cur + 1);
-    };
     auto load_chunk = [&](int ci) {
         int s = 0, c = ci;
         while (c >= J.nck[s]) c -= J.nck[s], ++s;
@@ -168,14 +130,12 @@ __global__ __launch_bounds__(256) void sg_gemm_kernel(const SgJobs jobs) {
     };
 
     const int nchunks = J.nck[0] + J.nck[1] + J.nck[2];
-    if (FAST) load_next(); else load_chunk(0);
+    load_chunk(0);
     store_chunk(0);
     __syncthreads();
     for (int ci = 0; ci < nchunks; ++ci) {
         const int buf = ci & 1;
-        if (ci + 1 < nchunks) {
-            if (FAST) load_next(); else load_chunk(ci + 1);
-        }
+        if (ci + 1 < nchunks) load_chunk(ci + 1);
         const float* Ab = &As[buf][wm * 32 + li];
         const float* Bb = &Bs[buf][wn * 32 + li];
 #pragma unroll
@@ -196,60 +156,28 @@ __global__ __launch_bounds__(256) void sg_gemm_kernel(const SgJobs jobs) {
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
             const int m = m0 + mb * 64 + wm * 32 + acc_row(r) + 4 * h;
-            if (FAST || (m < M && p < P)) dst[(size_t)m * ldp + p] = ob ? fmaf(acc[mb][r], alpha, ob[m]) : acc[mb][r] * alpha;
+            if (m < M && p < P) dst[(size_t)m * ldp + p] = ob ? fmaf(acc[mb][r], alpha, ob[m]) : acc[mb][r] * alpha;
         }
-    // Optional statistics epilogue (K6: the q / k projections feed a training-mode BatchNorm): the tile meets in LDS (the operand
-    // ring is dead behind the loop's last barrier), four threads walk one row -- 16 values each, sums of (d - pivot) and
-    // (d - pivot)^2 with the row's first value as pivot, so nothing cancels -- and two quad exchanges combine them.  Replaces the
-    // statistics launch (5 us + a launch boundary on a chain of dependent launches); measured in round 3 as 160 cross-lane
-    // shuffles per wave on the accumulator registers it cost 5 us, through LDS it is 16 stores + 16 loads per thread.
-    if constexpr (FAST) {
-        if (J.stat != nullptr) {
-            constexpr int TP = 65;   // pitch: the 16 rows x 4 segments a wave reads in one step fall in 64 different banks
-            float* T = &As[0][0];
-            static_assert(2 * SG_BK * (SG_T * MB + 4) >= SG_T * MB * TP, "the tile must fit the A ring");
-#pragma unroll
-            for (int mb = 0; mb < MB; ++mb)
-#pragma unroll
-                for (int r = 0; r < 16; ++r)
-                    T[(mb * 64 + wm * 32 + acc_row(r) + 4 * h) * TP + wn * 32 + li] = acc[mb][r] * alpha;
-            __syncthreads();
-#pragma unroll
-            for (int mb = 0; mb < MB; ++mb) {
-                const int row = mb * 64 + (tid >> 2), seg = tid & 3;
-                const float* tr = T + row * TP;
-                const float pivot = tr[0];
-                float s1 = 0.f, s2 = 0.f;
-#pragma unroll
-                for (int j = 0; j < 16; ++j) {
-                    const float d = tr[seg * 16 + j] - pivot;
-                    s1 += d, s2 = fmaf(d, d, s2);
-                }
-                s1 += __shfl_xor(s1, 1, 64), s2 += __shfl_xor(s2, 1, 64);
-                s1 += __shfl_xor(s1, 2, 64), s2 += __shfl_xor(s2, 2, 64);
-                if (seg == 0) {
-                    const float mean_d = s1 * (1.f / 64.f);
-                    f32x2 o = {pivot + mean_d, fmaxf(s2 - s1 * mean_d, 0.f)};
-                    *reinterpret_cast<f32x2*>(J.stat + (((size_t)(m0 + row) * jobs.B + b) * J.tiles_n + nt) * 2) = o;
-                }
-            }
-        }
-    }
 }
 
-// ---- round 6: the FAST form with a quarter / half of the LDS operand reads ------------------------------------
-// sg_gemm_kernel<MB, true> above reads TWO dwords from LDS per MFMA (one per operand and k-step: 32 ds_read_b32 for the 16 MFMAs of
-// a chunk at MB = 1), and on gfx950 those issue slots add up with the fp32 MFMAs of the three or four waves that share a SIMD
-// (20.8 us for the 1.6 GFLOP of the q / k / v projections: 0.49 of the matrix peak; five launches of this kernel per step).
+// ---- the fast kernel (round 6) ---------------------------------------------------------------------------------
+// Every job of the launch has full tiles (M % (64 MB) == 0, P % 64 == 0), whole chunks (every K-segment % 32 == 0), 16-byte
+// aligned rows and a k-major B.  Then the loader has no bounds logic, its per-thread offsets and the key-mean bias are computed
+// once, and the segment descriptor (kernarg scalar loads) is only touched when a K-segment ends.
+// Round 3's form of this kernel kept the generic kernel's LDS chunks and read TWO dwords from LDS per MFMA (one per operand and
+// k-step: 32 ds_read_b32 for the 16 MFMAs of a chunk at MB = 1), and on gfx950 those issue slots add up with the fp32 MFMAs of the
+// three or four waves that share a SIMD (20.8 us for the 1.6 GFLOP of the q / k / v projections: 0.49 of the matrix peak; five
+// launches of this kernel per step).
 // Which two k an MFMA step contracts is free as long as A and B agree, so step s takes k = s from lanes 0-31 and k = 16 + s from
 // lanes 32-63: the 16 values a lane needs of an operand are then
 //   * 16 CONSECUTIVE floats of its row when the operand is stored with the contracted index contiguous (a weight as PyTorch
 //     stores it: M-major A): image [row][32 k], pitch 36 (8-lane groups of a ds_read_b128 / ds_write_b128
-//     cover all 32 banks once) -- four 16-byte reads per chunk, written with 16-byte stores exactly as loaded (the old form
-//     transposed such an operand with scalar stores);
+//     cover all 32 banks once) -- four 16-byte reads per chunk, written with 16-byte stores exactly as loaded (the generic kernel
+//     transposes such an operand with scalar stores);
 //   * 16 rows 64 (or 128) floats apart when the operand is stored k-major (an activation (K, P), a weight used transposed):
 //     image [k][row], pitch = the tile width, read in pairs by ds_read2st64_b32 -- eight reads per chunk.
-// 8 .. 16 LDS reads per chunk and operand pair instead of 32; same loaders, same epilogues, same tile -> workgroup mapping.
+// 8 .. 16 LDS reads per chunk and operand pair instead of 32; the tile -> workgroup mapping and the output epilogue are the generic
+// kernel's.
 constexpr int SG_KP = 36;
 
 template <int MB>
@@ -268,7 +196,7 @@ __global__ __launch_bounds__(256) void sg_gemm_fast_kernel(const SgJobs jobs) {
     t /= J.tiles_n;
     const int mt = t % J.tiles_m, b = t / J.tiles_m;
     const int m0 = mt * MT, p0 = nt * SG_T, M = J.M, lda = J.lda, ldp = J.ldp;
-    const bool am = J.a_mmajor != 0;   // workgroup-uniform (B is k-major here: sg_gemm keeps position-major B jobs on the round-3 kernel)
+    const bool am = J.a_mmajor != 0;   // workgroup-uniform (B is k-major here: sg_gemm keeps position-major B jobs on the generic kernel)
 
     f32x16 acc[MB];
 #pragma unroll
@@ -374,9 +302,13 @@ __global__ __launch_bounds__(256) void sg_gemm_fast_kernel(const SgJobs jobs) {
             const int m = m0 + mb * 64 + wm * 32 + acc_row(r) + 4 * h;
             dst[(size_t)m * ldp + p] = ob ? fmaf(acc[mb][r], alpha, ob[m]) : acc[mb][r] * alpha;
         }
-    // statistics epilogue: as sg_gemm_kernel<MB, true> (the operand ring is dead behind the loop's last barrier)
+    // Optional statistics epilogue (K6: the q / k projections feed a training-mode BatchNorm): the tile meets in LDS (the operand
+    // ring is dead behind the loop's last barrier), four threads walk one row -- 16 values each, sums of (d - pivot) and
+    // (d - pivot)^2 with the row's first value as pivot, so nothing cancels -- and two quad exchanges combine them.  Replaces the
+    // statistics launch (5 us + a launch boundary on a chain of dependent launches); measured in round 3 as 160 cross-lane
+    // shuffles per wave on the accumulator registers it cost 5 us, through LDS it is 16 stores + 16 loads per thread.
     if (J.stat != nullptr) {
-        constexpr int TP = 65;
+        constexpr int TP = 65;   // pitch: the 16 rows x 4 segments a wave reads in one step fall in 64 different banks
         float* T = &As[0][0];
         static_assert(2 * A_FLOATS >= MT * TP, "the tile must fit the A ring");
 #pragma unroll
@@ -430,19 +362,14 @@ bool sg_gemm(SgJobs& jobs, int B, hipStream_t stream, int mb) {
         }
         j.tiles_m = ceil_div(j.M, MT), j.tiles_n = ceil_div(j.P, SG_T), j.tile_base = base;
         base += j.tiles_m * j.tiles_n * B;
-        bool f = j.vec && (j.M % MT) == 0 && (j.P % SG_T) == 0 && (j.lda & 3) == 0 && (!j.b_pmajor || (j.ldb & 3) == 0);
+        bool f = j.vec && (j.M % MT) == 0 && (j.P % SG_T) == 0 && (j.lda & 3) == 0 && !j.b_pmajor;   // no caller stages a position-major B today
         for (int s = 0; s < j.nseg; ++s)
             f = f && (j.seg[s].k % SG_BK) == 0 && (reinterpret_cast<uintptr_t>(j.seg[s].a) & 15) == 0 &&
                 (reinterpret_cast<uintptr_t>(j.seg[s].b) & 15) == 0;
         if (j.a_img_stride & 3) f = false;
         fast = fast && f;
     }
-    // CABINET_SG_KCONTIG=0: the round-3 FAST kernel (two LDS dwords per MFMA) for A/B timing
-    static const bool kc_env = [] { const char* e = getenv("CABINET_SG_KCONTIG"); return !(e && e[0] == '0'); }();
-    bool kcontig = kc_env;
-    for (int i = 0; i < jobs.n; ++i) kcontig = kcontig && !jobs.j[i].b_pmajor;   // no caller stages a position-major B today
-    auto kernel = mb == 2 ? (fast ? (kcontig ? sg_gemm_fast_kernel<2> : sg_gemm_kernel<2, true>) : sg_gemm_kernel<2, false>)
-                          : (fast ? (kcontig ? sg_gemm_fast_kernel<1> : sg_gemm_kernel<1, true>) : sg_gemm_kernel<1, false>);
+    auto kernel = mb == 2 ? (fast ? sg_gemm_fast_kernel<2> : sg_gemm_kernel<2>) : (fast ? sg_gemm_fast_kernel<1> : sg_gemm_kernel<1>);
     hipLaunchKernelGGL(kernel, dim3(base), dim3(256), 0, stream, jobs);
     return fast;
 }

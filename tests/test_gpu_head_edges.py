@@ -19,7 +19,6 @@ public wrapper, against the fp64 CPU oracle of the kernel's own test file.
 """
 import copy
 import itertools
-import os
 
 import pytest
 import torch
@@ -51,7 +50,7 @@ K11_CASES = {
     "nsplit-cut-to-chunks": ((1, 64, 0, 64, 5, 9), "odd1", "odd1", (3, 3)),         # 256 ranges wanted, three chunks there
 }
 K11_K128_RULE = (128, 64, 64, 256, 3, 34)    # two inputs, 256 ragged tile blocks (3 of 4 rows, 2 of 32 columns) x 2 = 512 workgroups
-# conv1x1 (B, Ci, Co, H, W) -> ceil(P / 128) * B * ceil(max(Ci, Co) / 128); >= 400 is the big-plane path (cab_qkv.hip:977-979)
+# conv1x1 (B, Ci, Co, H, W) -> ceil(P / 128) * B * ceil(max(Ci, Co) / 128); >= 400 is the big-plane path (cab_qkv.hip:894-896)
 C1_CASES = [((4, 24, 72, 101, 127), 404), ((4, 24, 72, 100, 127), 400), ((2, 128, 256, 100, 128), 400), ((4, 24, 72, 99, 128), 396)]
 # K5 (B, C, H, W) -> form, (TR, tiles per plane) of the tiled form
 K5_CASES = {
@@ -90,21 +89,21 @@ def _th(n):
 
 
 def _tile_blocks(B, H, W):
-    """conv3x3_tile_blocks (conv3x3_wino.hip:1285): blocks of 2 x 16 Winograd tiles = 4 x 32 pixels."""
+    """conv3x3_tile_blocks (conv3x3_wino.hip:1032): blocks of 2 x 16 Winograd tiles = 4 x 32 pixels."""
     return B * ((_th(H) + 1) // 2) * ((_th(W) + 15) // 16)
 
 
 def _wino_route(ntb, Kout, K0, W):
-    """wino_conv_run (conv3x3_wino.hip:1294-1351) with CABINET_WINO_128 / _NKB / _PAIR unset and 8-byte aligned operands; the data
-    gradient calls it with Kout = C0 + C1 and K0 = C0 (conv3x3_dgrad_run, :1374)."""
-    if W % 2 == 0 and Kout % 128 == 0 and K0 % 64 == 0 and ntb * (Kout // 128) >= 512:   # :1307-1309
+    """wino_conv_run (conv3x3_wino.hip:1041-1082) with CABINET_WINO_128 unset and 8-byte aligned operands; the data
+    gradient calls it with Kout = C0 + C1 and K0 = C0 (conv3x3_dgrad_run, :1102)."""
+    if W % 2 == 0 and Kout % 128 == 0 and K0 % 64 == 0 and ntb * (Kout // 128) >= 512:   # :1055-1057
         return "k128"
-    small = ntb * (Kout // 64) <= 200                                                    # :1334
-    return ("pair" if W % 2 == 0 else "odd") + ("1" if small else "2")                   # :1341, :1348-1351
+    small = ntb * (Kout // 64) <= 200                                                    # :1066
+    return ("pair" if W % 2 == 0 else "odd") + ("1" if small else "2")                   # :1050, :1076-1079
 
 
 def _wgrad_plan(B, C, K, H, W):
-    """wino_wgrad_nchunks / wino_wgrad_nsplit (conv3x3_wino.hip:1380-1386): chunks of 8 tiles of one tile row."""
+    """wino_wgrad_nchunks / wino_wgrad_nsplit (conv3x3_wino.hip:1108-1114): chunks of 8 tiles of one tile row."""
     nchunks = B * _th(H) * ((_th(W) + 7) // 8)
     units = (K // 64) * (C // 64)
     ns = max(1, 256 * (-(-units // 256)) // units)
@@ -112,7 +111,7 @@ def _wgrad_plan(B, C, K, H, W):
 
 
 def _conv1x1_product(B, Ci, Co, P):
-    """conv1x1_small (cab_qkv.hip:977-979): the small-tile path below 400."""
+    """conv1x1_small (cab_qkv.hip:894-896): the small-tile path below 400."""
     return -(-P // 128) * B * -(-max(Ci, Co) // 128)
 
 
@@ -121,7 +120,7 @@ def _k16(n):
 
 
 def _sd_plan(B, M, N, P):
-    """sd_plan of small_gemm.hip:579-608 for ONE job (tiles_total = its own tiles) -> (total chunks, chunks per split, splits)."""
+    """sd_plan of small_gemm.hip:506-535 for ONE job (tiles_total = its own tiles) -> (total chunks, chunks per split, splits)."""
     tiles = -(-M // 64) * -(-N // 64)
     total = B * -(-P // 32)
     nsplit = max(1, min(-(-total // 8), -(-1024 // tiles), 64))
@@ -149,8 +148,8 @@ def _local_lds_bwd(B, H, W):
 def _qkv_plan(B, C, Kc, Vc, H, W, sizes):
     """The three independent predicates of K6 for training mode and 16-byte aligned operands."""
     P = H * W
-    # sg_gemm (small_gemm.hip:418-447) returns `fast` for the three projection jobs: whole 64 x 64 tiles and whole 32-deep chunks;
-    # qkv_fwd_run (cab_qkv.hip:820-824) then takes the BatchNorm partials from the GEMM's epilogue
+    # sg_gemm (small_gemm.hip:350-375) returns `fast` for the three projection jobs: whole 64 x 64 tiles and whole 32-deep chunks;
+    # qkv_fwd_run (cab_qkv.hip:742-746) then takes the BatchNorm partials from the GEMM's epilogue
     stats_in_gemm = P % 4 == 0 and Kc % 64 == 0 and Vc % 64 == 0 and P % 64 == 0 and C % 32 == 0 and C % 4 == 0
     # qkv_fused_fwd_supported (cab_qkv_fused.hip:259-266); the LDS bound does not bind at these sizes
     fused = Kc % 32 == 0 and Vc % 32 == 0 and P % 256 == 0 and Kc == Vc and Kc in (64, 128, 256) and all(s * s <= 64 for s in sizes)
@@ -240,7 +239,6 @@ def test_head_plan_cases_reach_their_branches():
 # ------------------------------------------------------------------------------------------------ shared pieces
 def _no_wino_env(monkeypatch):
     monkeypatch.delenv("CABINET_WINO_128", raising=False)
-    assert "CABINET_WINO_NKB" not in os.environ and "CABINET_WINO_PAIR" not in os.environ   # read once per process
 
 
 def _k11_dev(x0, x1, w, dy, with_part=False):

@@ -52,7 +52,7 @@ def make_case(B, C, Hl, Wl, H, W, seed, zero_class=None):
 
 
 class kernel_choice:
-    """CABINET_OHEM_SEGMENT_KERNEL / CABINET_OHEM_BAND for the duration of a block (the library reads them per call)."""
+    """CABINET_OHEM_SEGMENT_KERNEL for the duration of a block (the library reads it per call)."""
 
     def __init__(self, var):
         self.var = var
@@ -131,7 +131,7 @@ OTHER = [
     (2, 5, 10, 6, 20, 48),       # x2 rows, x8 columns, 5 classes (predicated bucket of 8)
     (1, 19, 16, 24, 64, 96),     # x4: general column pass, 19 classes
 ]
-CASES = [(s, None) for s in ROW + OTHER] + [(s, "CABINET_OHEM_SEGMENT_KERNEL") for s in ROW] + [(s, "CABINET_OHEM_BAND") for s in ROW]
+CASES = [(s, None) for s in ROW + OTHER] + [(s, "CABINET_OHEM_SEGMENT_KERNEL") for s in ROW]
 
 
 @pytest.mark.parametrize("shape,env", CASES)
@@ -301,8 +301,7 @@ def test_graphed_ddp_step_world1_with_class_weights():
 
 # ---- 4. unit weights are the unweighted kernels' bits -----------------------------------------------------------------------
 
-@pytest.mark.parametrize("shape,env", [(s, None) for s in ROW[:3] + OTHER[:1] + OTHER[3:4]] + [(ROW[1], "CABINET_OHEM_SEGMENT_KERNEL"),
-                                                                                               (ROW[1], "CABINET_OHEM_BAND")])
+@pytest.mark.parametrize("shape,env", [(s, None) for s in ROW[:3] + OTHER[:1] + OTHER[3:4]] + [(ROW[1], "CABINET_OHEM_SEGMENT_KERNEL")])
 def test_unit_weights_are_bitwise_the_unweighted_result(shape, env):
     B, C, Hl, Wl, H, W = shape
     low, low2, lab, w = make_case(*shape, seed=H + C + 1)
@@ -328,8 +327,7 @@ def test_unit_weights_are_bitwise_the_unweighted_result(shape, env):
 
 # ---- 5. weight 0 ------------------------------------------------------------------------------------------------------------
 
-@pytest.mark.parametrize("shape,env", [(ROW[1], None), (ROW[1], "CABINET_OHEM_SEGMENT_KERNEL"), (ROW[1], "CABINET_OHEM_BAND"),
-                                       (OTHER[3], None)])
+@pytest.mark.parametrize("shape,env", [(ROW[1], None), (ROW[1], "CABINET_OHEM_SEGMENT_KERNEL"), (OTHER[3], None)])
 def test_a_class_of_weight_zero(shape, env):
     B, C, Hl, Wl, H, W = shape
     low, _, lab, w = make_case(*shape, seed=H + C + 2, zero_class=2)

@@ -29,13 +29,11 @@ for c in (3, 5):
 # ---- K11: the 128-channel kernel against the 64-channel kernel and MIOpen, same box, same tensors
 { echo "== default (conv_out: 128 channels per workgroup, one wave per SIMD)"; python tools/time_conv3x3.py 2>&1 | grep -v "$F";
   echo "== CABINET_WINO_128=0 (round 5: 64 channels per workgroup)"; CABINET_WINO_128=0 python tools/time_conv3x3.py 2>&1 | grep "conv_out";
-  echo "== CABINET_WINO_128=2 (persistent form, register epilogue)"; CABINET_WINO_128=2 python tools/time_conv3x3.py 2>&1 | grep "conv_out";
   echo "== config 5"; python tools/time_conv3x3.py --config5 --no-check 2>&1 | grep -v "$F";
   echo "== config 5, CABINET_WINO_128=0"; CABINET_WINO_128=0 python tools/time_conv3x3.py --config5 --no-check 2>&1 | grep "conv_out"; } > $O/${TAG}_conv3x3_ab.log
 tail -30 $O/${TAG}_conv3x3_ab.log | cut -c1-170
-# ---- the CAB's launch chain; small-GEMM core with k-contiguous operand images against round 3's
+# ---- the CAB's launch chain
 { echo "== config 3 grid (8 x 256 x 32 x 32)"; python tools/time_cab_chain.py 2>&1 | grep -v "$F";
-  echo "== CABINET_SG_KCONTIG=0 (round-3 small-GEMM core: two LDS dwords per MFMA)"; CABINET_SG_KCONTIG=0 python tools/time_cab_chain.py 2>&1 | grep "K6 \|project_out\|whole block";
   echo "== config 5 grid (2 x 256 x 64 x 32)"; python tools/time_cab_chain.py 2 64 32 2>&1 | grep -v "$F"; } > $O/${TAG}_cab_chain.txt
 cat $O/${TAG}_cab_chain.txt | cut -c1-120
 # ---- the data-parallel step at world size 1 with RCCL forced: both replay schedules
@@ -45,7 +43,7 @@ cat $O/${TAG}_cab_chain.txt | cut -c1-120
   echo "bench.py, single-GPU step (GraphedTrainStep): $(python bench.py --no-cpu-baseline --no-kernel-roofline --no-eval-forward 2>/dev/null | python -c 'import json,sys; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print(d["value"], "images/s", d["ms_per_step"], "ms/step")')"; } > $O/${TAG}_ddp_segments.txt
 cat $O/${TAG}_ddp_segments.txt | cut -c1-200
 # ---- same-box A/B of the step: round-6 switches off one at a time
-for sw in CABINET_WINO_128 CABINET_FFM_EXACT_MASK CABINET_SG_KCONTIG; do
+for sw in CABINET_WINO_128 CABINET_FFM_EXACT_MASK; do
   echo "$sw=0: $(env $sw=0 python bench.py --no-cpu-baseline --no-kernel-roofline --no-eval-forward 2>/dev/null | python -c 'import json,sys; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print(d["value"], "images/s", d["ms_per_step"], "ms/step")')"
 done > $O/${TAG}_step_ab.txt
 echo "defaults: $(python bench.py --no-cpu-baseline --no-kernel-roofline --no-eval-forward 2>/dev/null | python -c 'import json,sys; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print(d["value"], "images/s", d["ms_per_step"], "ms/step")')" >> $O/${TAG}_step_ab.txt
