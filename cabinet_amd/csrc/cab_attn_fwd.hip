@@ -464,9 +464,11 @@ __global__ __launch_bounds__(512) void cab_attn_fwd_w8_kernel(
     // channel 8j + 4h + e: a lane's operands are 16-byte quads of ITS row)
     f32x4 wq[PROJ ? VC / 8 : 1];
     if constexpr (PROJ) {
-        const float* wrow = w_out + (size_t)(wave * 32 + li) * VC + 4 * h;
+        if (wave * 32 < Co) {   // a wave past the last output block owns none: its rows would lie behind the end of w_out
+            const float* wrow = w_out + (size_t)(wave * 32 + li) * VC + 4 * h;
 #pragma unroll
-        for (int j = 0; j < VC / 8; ++j) wq[j] = *reinterpret_cast<const f32x4*>(wrow + 8 * j);
+            for (int j = 0; j < VC / 8; ++j) wq[j] = *reinterpret_cast<const f32x4*>(wrow + 8 * j);
+        }
     }
     __syncthreads();
     float ms = -INFINITY, lt = 0.f;

@@ -45,6 +45,7 @@ hipError_t ffm_fwd_run(const FfmShape& s, const float* fsp, const float* fcp, co
                        hipStream_t stream);
 size_t ffm_up_fwd_workspace(const FfmShape& s, int Hl, int Wl);
 size_t ffm_up_bwd_workspace(const FfmShape& s, int Hl, int Wl);
+size_t ffm_up_bwd_adjoint_lds(const FfmShape& s, int Hl, int Wl, size_t* limit, int* band_rows);
 hipError_t ffm_up_fwd_run(const FfmShape& s, int Hl, int Wl, const float* fsp, const float* low,
                           const float* w_blk, const float* bn_w, const float* bn_b, float* run_mean,
                           float* run_var, const float* w1, const float* w2, int training, float momentum,
@@ -426,6 +427,13 @@ int cabinet_ffm_up_bwd(const float* dout, const float* fsp, const float* low, co
         !save_invstd || !pooled || !gate || !dfsp || !dlow || !dw_blk || !dbn_weight || !dbn_bias || !dw1 || !dw2)
         return fail(CABINET_ERR_INVALID_ARG, "ffm_up_bwd: null tensor pointer");
     CABINET_REQUIRE_ALIGNED("ffm_up_bwd", dout, fsp, low, w_blk, z, dfsp, dlow, dw_blk);
+    size_t lds_limit = 0;
+    int band_rows = 0;
+    if (const size_t lds = cabinet::ffm_up_bwd_adjoint_lds({B, Cs, Cc, Co, Cm, H, W}, Hl, Wl, &lds_limit, &band_rows); lds > lds_limit)
+        return fail(CABINET_ERR_UNSUPPORTED,
+                    "ffm_up_bwd: the resize %dx%d -> %dx%d is refused: one band of %d low-resolution rows of the resize adjoint would "
+                    "stage %zu bytes of LDS (limit %zu); the staged band grows with H/Hl x W",
+                    Hl, Wl, H, W, band_rows, lds, lds_limit);
     const size_t need = cabinet_ffm_up_bwd_workspace_bytes(B, Cs, Cc, Co, Cm, H, W, Hl, Wl);
     if (need && (!workspace || workspace_bytes < need))
         return fail(CABINET_ERR_WORKSPACE, "ffm_up_bwd: workspace %zu < %zu bytes", workspace_bytes, need);

@@ -1452,6 +1452,34 @@ hipError_t ffm_bwd_run(const FfmShape& s, const float* dout, const float* fsp, c
     return dw_product(dz, fcp, s.B, s.Co, s.Cc, P, part, dw_blk, Cin, s.Cs, stream);
 }
 
+// geometry of upsample_adjoint_kernel for one resize: staged rows per band, horizontal taps, de-interleave factor, LDS bytes
+struct AdjGeom {
+    int max_rows, XT, R, plane;
+    size_t lds;
+};
+static AdjGeom adj_geom(int H, int W, int Hl, int Wl) {
+    AdjGeom g{};
+    g.max_rows = (int)((ADJ_BAND + 2) * ((float)H / (float)Hl)) + 6, g.XT = adj_xtaps(W, Wl);
+    // de-interleave factor of the horizontal pass: the integer resize ratio (the model's x4), else 1 (plain layout)
+    g.R = (Wl > 0 && W % Wl == 0 && W / Wl <= 32) ? W / Wl : 1;
+    g.plane = ceil_div(W, g.R);
+    const int want = (g.R & (g.R - 1)) == 0 ? 32 / g.R : 1;  // phase stride in banks (see the kernel header)
+    g.plane += (want - g.plane % 32 + 32) % 32;
+    g.lds = ((size_t)g.max_rows * W + (size_t)ADJ_BAND * g.R * g.plane + (size_t)ADJ_BAND * g.max_rows + (size_t)2 * Wl * g.XT +
+             ADJ_BAND) * sizeof(float);
+    return g;
+}
+static bool ffm_up_bwd_lin_adj(int H, int W, int Hl, int Wl) {
+    return H >= Hl && ffm_bwd_adj_enabled() && ffm_bwd_adj_supported(H, W, Hl, Wl);
+}
+// LDS bytes one band of the resize adjoint stages in the backward of this geometry; 0 where the backward does not run that kernel.
+// Above `limit` (ADJ_LDS_MAX) ffm_up_bwd_run refuses the geometry; the C entry point asks first, so that nothing is launched for it.
+constexpr size_t ADJ_LDS_MAX = (size_t)160 * 1024;
+size_t ffm_up_bwd_adjoint_lds(const FfmShape& s, int Hl, int Wl, size_t* limit, int* band_rows) {
+    *limit = ADJ_LDS_MAX, *band_rows = ADJ_BAND;
+    return ffm_up_bwd_lin_adj(s.H, s.W, Hl, Wl) ? 0 : adj_geom(s.H, s.W, Hl, Wl).lds;
+}
+
 hipError_t ffm_up_bwd_run(const FfmShape& s, int Hl, int Wl, const float* dout, const float* fsp,
                           const float* low, const float* w_blk, const float* bn_w, const float* bn_b,
                           const float* w1, const float* w2, const float* z, const float* save_mean,
@@ -1465,9 +1493,10 @@ hipError_t ffm_up_bwd_run(const FfmShape& s, int Hl, int Wl, const float* dout, 
     float* part = reinterpret_cast<float*>(base + L.part);
     float* dzl = reinterpret_cast<float*>(base + L.dzl);
     // the band decomposition must cover every output row exactly once and fit the staging buffer
-    const int max_rows = (int)((ADJ_BAND + 2) * ((float)s.H / (float)Hl)) + 6, XT = adj_xtaps(s.W, Wl);
+    const AdjGeom ag = adj_geom(s.H, s.W, Hl, Wl);
+    const int max_rows = ag.max_rows, XT = ag.XT;
     const bool fuse_dz = s.H >= Hl;  // an upsample (the model's x4); shrinking resizes keep the two-pass form
-    const bool lin_adj = fuse_dz && ffm_bwd_adj_enabled() && ffm_bwd_adj_supported(s.H, s.W, Hl, Wl);
+    const bool lin_adj = ffm_up_bwd_lin_adj(s.H, s.W, Hl, Wl);
     const bool fused_xw = fuse_dz && ffm_bwd_fused_enabled() && ffm_bwd_fused_supported(s.B, s.Cs, s.Cc, s.Co, P, Pl);
     const bool dz_in_xw = lin_adj && fused_xw;   // nothing but the fused kernel reads dz: it forms it from (dout, z) itself
     // lin_adj: dz_low from adjoint fields taken in the reduction pass (ffm_bwd_adj.hip)
@@ -1477,21 +1506,16 @@ hipError_t ffm_up_bwd_run(const FfmShape& s, int Hl, int Wl, const float* dout, 
         return e;
     // dz_low = U^T dz  (adjoint of the bilinear upsample), then everything on the Cc side is low resolution
     if (!lin_adj) {
-        // de-interleave factor of the horizontal pass: the integer resize ratio (the model's x4), else 1 (plain layout)
-        const int R = (Wl > 0 && s.W % Wl == 0 && s.W / Wl <= 32) ? s.W / Wl : 1;
-        int plane = ceil_div(s.W, R);
-        const int want = (R & (R - 1)) == 0 ? 32 / R : 1;  // phase stride in banks (see the kernel header)
-        plane += (want - plane % 32 + 32) % 32;
-        const size_t lds = ((size_t)max_rows * s.W + (size_t)ADJ_BAND * R * plane + (size_t)ADJ_BAND * max_rows +
-                            (size_t)2 * Wl * XT + ADJ_BAND) * sizeof(float);
+        const int R = ag.R, plane = ag.plane;
+        const size_t lds = ag.lds;
         // the staged band grows with the resize ratio: the attribute is set to the device maximum once (per device), so
         // that a small first call cannot pin it below what a later, larger geometry needs
         static lds_attr_mask mask_fused{0}, mask_plain{0};
-        if (lds > 160 * 1024) return hipErrorInvalidValue;
-        if (hipError_t e = ensure_dynamic_lds(reinterpret_cast<const void*>(upsample_adjoint_kernel<true>), 160 * 1024, mask_fused);
+        if (lds > ADJ_LDS_MAX) return hipErrorInvalidValue;
+        if (hipError_t e = ensure_dynamic_lds(reinterpret_cast<const void*>(upsample_adjoint_kernel<true>), ADJ_LDS_MAX, mask_fused);
             e != hipSuccess)
             return e;
-        if (hipError_t e = ensure_dynamic_lds(reinterpret_cast<const void*>(upsample_adjoint_kernel<false>), 160 * 1024, mask_plain);
+        if (hipError_t e = ensure_dynamic_lds(reinterpret_cast<const void*>(upsample_adjoint_kernel<false>), ADJ_LDS_MAX, mask_plain);
             e != hipSuccess)
             return e;
         DzArgs da{};
