@@ -7,6 +7,7 @@
 * ``cabinet_amd.ddp``        bucketed RCCL gradient all-reduce overlapped with backward
 * ``cabinet_amd.train``      the reference's train step (train.py:429-441) as a harness
 * ``cabinet_amd.evaluate``   the reference's multi-scale evaluator (mIoU) with its probability tail in HIP kernels
+* ``cabinet_amd.predict``    the reference's single-image inference and visualisation with the label / render tail in HIP kernels
 """
 import os as _os
 

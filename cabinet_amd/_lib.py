@@ -117,6 +117,10 @@ SIGNATURES = {
     "cabinet_eval_chip_accum": (_INT, [_PTR] * 2 + [_INT] * 6 + [_PTR] + [_INT] * 4 + [_PTR] * 2 + [_PTR]),
     "cabinet_eval_scale_merge": (_INT, [_PTR] + [_INT] * 8 + [_PTR] + [_INT] * 2 + [_PTR]),
     "cabinet_eval_argmax_hist": (_INT, [_PTR] * 2 + [_INT] * 5 + [_PTR] * 2 + [_PTR]),
+    "cabinet_predict_up_argmax_supported": (_INT, [_INT] * 5),
+    "cabinet_predict_up_argmax": (_INT, [_PTR] + [_INT] * 6 + [_PTR] + [_PTR]),
+    "cabinet_predict_argmax": (_INT, [_PTR] + [_INT] * 4 + [_PTR] + [_PTR]),
+    "cabinet_predict_render": (_INT, [_PTR] * 3 + [_INT] + [_PTR] * 2 + [_FLT] + [_INT] * 3 + [_PTR] * 3 + [_PTR]),
     "cabinet_se_act_bwd_workspace_bytes": (_SZ, [_INT] * 3),
     "cabinet_se_act_bwd_reduce": (_INT, [_PTR] * 8 + [_INT] * 4 + [_PTR] * 2 + [_PTR, _SZ, _PTR]),
     "cabinet_se_act_bwd_coef": (_INT, [_PTR] * 3 + [_INT] * 4 + [_PTR] * 4 + [_PTR]),

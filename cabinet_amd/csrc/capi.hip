@@ -175,6 +175,13 @@ hipError_t eval_scale_merge_run(const float* prob, int N, int C, int FH, int FW,
                                 int H, int W, hipStream_t stream);
 hipError_t eval_argmax_hist_run(const float* total, const long long* labels, int N, int C, int H, int W, int ignore_lb, long long* hist,
                                 unsigned char* pred, hipStream_t stream);
+// predict_tail.hip
+int predict_up_threads(int C, int wl, int W);
+hipError_t predict_up_argmax_run(const float* a, int N, int C, int hl, int wl, int H, int W, unsigned char* labels, hipStream_t stream);
+hipError_t predict_argmax_run(const float* total, int N, int C, int H, int W, unsigned char* labels, hipStream_t stream);
+hipError_t predict_render_run(const unsigned char* labels, const float* image, const unsigned char* palette, int n_colors,
+                              const float* mean, const float* std, float alpha, int N, int H, int W, unsigned char* pred,
+                              unsigned char* inp, unsigned char* ovl, hipStream_t stream);
 // opt_tail.hip
 size_t sgd_tail_workspace(int n_chunks);
 size_t sgd_tail_state(int n_entries);
@@ -1369,6 +1376,51 @@ int cabinet_eval_argmax_hist(const float* total, const long long* labels, int N,
     if (reinterpret_cast<uintptr_t>(pred) & 3) return fail(CABINET_ERR_INVALID_ARG, "eval_argmax_hist: pred must be 4-byte aligned");
     return hip_status(cabinet::eval_argmax_hist_run(total, labels, N, C, H, W, ignore_lb, hist, pred, static_cast<hipStream_t>(stream)),
                       "eval_argmax_hist launch");
+}
+
+// ------------------------------------------------------------------ inference tail (K17)
+int cabinet_predict_up_argmax_supported(int C, int hl, int wl, int H, int W) {
+    if (C < 1 || C > 32 || hl < 1 || wl < 1 || H < 1 || W < 1 || H > 65535) return 0;
+    return cabinet::predict_up_threads(C, wl, W) > 0 ? 1 : 0;
+}
+
+int cabinet_predict_up_argmax(const float* logits_low, int N, int C, int hl, int wl, int H, int W, unsigned char* labels,
+                              cabinet_stream_t stream) {
+    if (N <= 0 || C <= 0 || hl <= 0 || wl <= 0 || H <= 0 || W <= 0)
+        return fail(CABINET_ERR_INVALID_ARG, "predict_up_argmax: non-positive dimension");
+    if (!logits_low || !labels) return fail(CABINET_ERR_INVALID_ARG, "predict_up_argmax: null tensor pointer");
+    if (reinterpret_cast<uintptr_t>(logits_low) & 3) return fail(CABINET_ERR_INVALID_ARG, "predict_up_argmax: logits must be 4-byte aligned");
+    if (C > 32) return fail(CABINET_ERR_UNSUPPORTED, "predict_up_argmax: C=%d classes (max 32)", C);
+    if (N > 65535 || H > 65535) return fail(CABINET_ERR_UNSUPPORTED, "predict_up_argmax: N or H exceeds grid limits");
+    if (!cabinet_predict_up_argmax_supported(C, hl, wl, H, W))
+        return fail(CABINET_ERR_UNSUPPORTED, "predict_up_argmax: C=%d x resize ratio %d/%d exceeds the LDS row buffer", C, wl, W);
+    return hip_status(cabinet::predict_up_argmax_run(logits_low, N, C, hl, wl, H, W, labels, static_cast<hipStream_t>(stream)),
+                      "predict_up_argmax launch");
+}
+
+int cabinet_predict_argmax(const float* total, int N, int C, int H, int W, unsigned char* labels, cabinet_stream_t stream) {
+    if (N <= 0 || C <= 0 || H <= 0 || W <= 0) return fail(CABINET_ERR_INVALID_ARG, "predict_argmax: non-positive dimension");
+    if (!total || !labels) return fail(CABINET_ERR_INVALID_ARG, "predict_argmax: null tensor pointer");
+    if (C > 32) return fail(CABINET_ERR_UNSUPPORTED, "predict_argmax: C=%d classes (max 32)", C);
+    if (N > 65535) return fail(CABINET_ERR_UNSUPPORTED, "predict_argmax: N exceeds grid limits");
+    CABINET_REQUIRE_ALIGNED("predict_argmax", total);
+    return hip_status(cabinet::predict_argmax_run(total, N, C, H, W, labels, static_cast<hipStream_t>(stream)), "predict_argmax launch");
+}
+
+int cabinet_predict_render(const unsigned char* labels, const float* image, const unsigned char* palette, int n_colors,
+                           const float* mean, const float* std, float alpha, int N, int H, int W, unsigned char* pred_rgb,
+                           unsigned char* input_rgb, unsigned char* overlay_rgb, cabinet_stream_t stream) {
+    if (N <= 0 || H <= 0 || W <= 0) return fail(CABINET_ERR_INVALID_ARG, "predict_render: non-positive dimension");
+    if (!labels || !palette || !pred_rgb) return fail(CABINET_ERR_INVALID_ARG, "predict_render: null labels, palette or pred_rgb");
+    if (n_colors < 1 || n_colors > 256) return fail(CABINET_ERR_INVALID_ARG, "predict_render: n_colors=%d outside [1, 256]", n_colors);
+    if ((input_rgb || overlay_rgb) && !(image && mean && std))
+        return fail(CABINET_ERR_INVALID_ARG, "predict_render: input_rgb / overlay_rgb need the image with its mean and std");
+    if (!(alpha >= 0.f && alpha <= 1.f)) return fail(CABINET_ERR_INVALID_ARG, "predict_render: alpha=%g outside [0, 1]", (double)alpha);
+    if (reinterpret_cast<uintptr_t>(image) & 3) return fail(CABINET_ERR_INVALID_ARG, "predict_render: image must be 4-byte aligned");
+    if ((size_t)N * H * W > ((size_t)1 << 33)) return fail(CABINET_ERR_UNSUPPORTED, "predict_render: more than 2^33 pixels");
+    return hip_status(cabinet::predict_render_run(labels, image, palette, n_colors, mean, std, alpha, N, H, W, pred_rgb, input_rgb,
+                                                  overlay_rgb, static_cast<hipStream_t>(stream)),
+                      "predict_render launch");
 }
 
 // ------------------------------------------------------ optimizer tail (K16): clip + warm-up / poly SGD + EMA

@@ -12,6 +12,8 @@
 OHEM head           src/utils/loss.py:51-80 + cabinet.py:240-245          (``ohem_up_*``, used by cabinet_amd.loss)
 evaluation tail     src/scripts/evaluate.py:69-159, :193-226              (K13: ``eval_chip_accum`` / ``eval_scale_merge`` /
                     ``eval_argmax_hist``, no autograd; used by cabinet_amd.evaluate)
+inference tail      src/scripts/visualize.py:50-61, :113-139, :165-177    (K17: ``predict_up_argmax`` / ``predict_argmax`` /
+                    ``predict_render``, no autograd; used by cabinet_amd.predict)
 
 ONE dispatch rule for every operator here:
   * device tensor, shape inside the kernel family's coverage (each family exports ``*_supported``): the hand-written
@@ -1864,3 +1866,100 @@ def eval_argmax_hist(total, labels, hist, ignore_label, want_pred=False):
                                           _stream_handle(dev))
     _lib.check(rc, "cabinet_eval_argmax_hist")
     return pred
+
+
+# --------------------------------------------------------------------------- inference tail (K17; no autograd)
+
+
+def _u8_out(out, shape, device, what):
+    """The uint8 output of a K17 kernel: a fresh tensor, or the caller's (any byte offset into its storage; dense)."""
+    if out is None:
+        return torch.empty(shape, dtype=torch.uint8, device=device)
+    if not (out.dtype == torch.uint8 and out.device == device and tuple(out.shape) == tuple(shape) and out.is_contiguous()):
+        raise RuntimeError(f"{what}: out must be a dense uint8 tensor of shape {tuple(shape)} on the input's device")
+    return out
+
+
+def predict_up_argmax_supported(logits, size):
+    """True when ``predict_up_argmax`` takes these low-resolution logits: a device tensor, at most 32 classes, and the source
+    rows of one row segment fit the LDS (every model-resolution-to-image ratio <= 1 does)."""
+    if not (logits.is_cuda and logits.dim() == 4 and _lib.available()):
+        return False
+    N, C, hl, wl = logits.shape
+    return bool(N <= 65535 and _lib.load().cabinet_predict_up_argmax_supported(C, hl, wl, int(size[0]), int(size[1])))
+
+
+def predict_up_argmax(logits, size, out=None):
+    """(N, H, W) uint8 argmax over classes of F.interpolate(logits, size, mode="bilinear", align_corners=False) -- reference
+    visualize.py:113-114 and :139 with the model's final upsample (cabinet.py:240-245) for ``scales=[1.0]``, ``flip=False``:
+    softmax does not move the argmax, and the full-resolution class tensor is never built.  Lowest index on equal values."""
+    lib = _lib.load()
+    if not (logits.is_cuda and logits.dim() == 4):
+        raise RuntimeError("predict_up_argmax: logits must be a (N, C, h, w) device tensor")
+    a = _f32c(logits)
+    N, C, hl, wl = a.shape
+    H, W = int(size[0]), int(size[1])
+    labels = _u8_out(out, (N, H, W), a.device, "predict_up_argmax")
+    dev = a.device
+    with torch.cuda.device(dev):
+        rc = lib.cabinet_predict_up_argmax(_ptr(a), N, C, hl, wl, H, W, _ptr(labels), _stream_handle(dev))
+    _lib.check(rc, "cabinet_predict_up_argmax")
+    return labels
+
+
+def predict_argmax_supported(total):
+    return bool(total.is_cuda and total.dim() == 4 and _lib.available() and total.shape[1] <= 32 and total.shape[0] <= 65535)
+
+
+def predict_argmax(total, out=None):
+    """(N, H, W) uint8 ``torch.argmax(total, 1)`` of a (N, C, H, W) fp32 device tensor (reference visualize.py:139 on the
+    multi-scale / flip path), lowest index on equal values."""
+    lib = _lib.load()
+    if not (total.is_cuda and total.dim() == 4):
+        raise RuntimeError("predict_argmax: total must be a (N, C, H, W) device tensor")
+    t = _f32c(total)
+    N, C, H, W = t.shape
+    labels = _u8_out(out, (N, H, W), t.device, "predict_argmax")
+    dev = t.device
+    with torch.cuda.device(dev):
+        rc = lib.cabinet_predict_argmax(_ptr(t), N, C, H, W, _ptr(labels), _stream_handle(dev))
+    _lib.check(rc, "cabinet_predict_argmax")
+    return labels
+
+
+def predict_render(labels, image, palette, mean=(0.485, 0.456, 0.406), std=(0.229, 0.224, 0.225), alpha=0.6,
+                   want_input=True, want_overlay=True, out=None):
+    """The reference's colouring and blending (visualize.py:50-61, :165-177) on the device, byte for byte.
+
+    ``labels`` (N, H, W) uint8, ``image`` (N, 3, H, W) normalised fp32 or None, ``palette`` (n_colors, 3) uint8 on the device.
+    Returns a dict of (N, H, W, 3) uint8 tensors: ``pred`` = palette[min(label, n_colors - 1)] always; with an image ``input`` =
+    uint8(clip(image * std + mean, 0, 1) * 255) and ``overlay`` = Image.blend(input, pred, alpha), each unless switched off.
+    ``out`` may name caller-owned tensors under the same keys."""
+    lib = _lib.load()
+    if not (labels.is_cuda and labels.dtype == torch.uint8 and labels.dim() == 3 and labels.is_contiguous()):
+        raise RuntimeError("predict_render: labels must be a dense (N, H, W) uint8 device tensor")
+    N, H, W = labels.shape
+    dev = labels.device
+    if not (palette.dtype == torch.uint8 and palette.dim() == 2 and palette.shape[1] == 3 and palette.device == dev
+            and 1 <= palette.shape[0] <= 256):
+        raise RuntimeError("predict_render: palette must be a (n_colors <= 256, 3) uint8 tensor on labels' device")
+    palette = palette.contiguous()
+    img = None
+    if image is not None:
+        if tuple(image.shape) != (N, 3, H, W) or image.device != dev:
+            raise RuntimeError(f"predict_render: image {tuple(image.shape)} does not match labels {tuple(labels.shape)}")
+        img = _f32c(image)
+    want_input, want_overlay = bool(want_input and img is not None), bool(want_overlay and img is not None)
+    out = out or {}
+    res = {"pred": _u8_out(out.get("pred"), (N, H, W, 3), dev, "predict_render")}
+    if want_input:
+        res["input"] = _u8_out(out.get("input"), (N, H, W, 3), dev, "predict_render")
+    if want_overlay:
+        res["overlay"] = _u8_out(out.get("overlay"), (N, H, W, 3), dev, "predict_render")
+    m3, s3 = (_ct.c_float * 3)(*[float(v) for v in mean]), (_ct.c_float * 3)(*[float(v) for v in std])
+    with torch.cuda.device(dev):
+        rc = lib.cabinet_predict_render(_ptr(labels), _ptr(img if (want_input or want_overlay) else None), _ptr(palette),
+                                        int(palette.shape[0]), _ct.addressof(m3), _ct.addressof(s3), float(alpha), N, H, W,
+                                        _ptr(res["pred"]), _ptr(res.get("input")), _ptr(res.get("overlay")), _stream_handle(dev))
+    _lib.check(rc, "cabinet_predict_render")
+    return res

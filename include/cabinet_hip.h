@@ -607,6 +607,38 @@ int cabinet_eval_argmax_hist(const float* total, const long long* labels, int N,
                              unsigned char* pred, cabinet_stream_t stream);
 
 /* ------------------------------------------------------------------------- *
+ * Inference tail (K17; ADDITIVE to ABI version 8: no existing entry point, constant or layout changes).
+ * Replaces, for one image or a batch, what src/scripts/visualize.py does after the model: :114-139 (softmax, flip, resize,
+ * +=, /=, argmax, the copy of int64 labels to the host) together with the model's final x8 upsample (cabinet.py:240-245),
+ * :50-61 (colorize_mask) and :165-177 (de-normalise, clip, * 255, astype(uint8), Image.blend).
+ * Every output is a byte array; neither its start nor its row starts need be dword-aligned, and no byte outside it is written.
+ *
+ * cabinet_predict_up_argmax -- visualize.py:113-114 + :139 for scales = [1.0], flip = False, with cabinet.py:240-245:
+ *   labels (N,H,W) uint8 [n,y,x] = argmax over c of the bilinear resize of logits_low (N,C,hl,wl) to (H,W)
+ *   (align_corners=False, ratios hl/H and wl/W, PyTorch's source-index rule; at ratio 1 the logits themselves are compared).
+ *   softmax is monotonic per pixel, so this is the argmax of the reference's probabilities; the full-resolution class tensor
+ *   never exists.  Strict `>`: the lowest index wins among equal values (torch.argmax); a NaN logit is never chosen.
+ *   C <= 32 (8 and 19 are compiled forms); supported when the staged source rows of one row segment fit the LDS
+ *   (every ratio wl/W <= 1 does; a strongly shrinking resize of many classes is refused).
+ * cabinet_predict_argmax -- visualize.py:139 for the multi-scale / flip path: labels (N,H,W) uint8 = argmax over c of
+ *   total (N,C,H,W) fp32 (16-byte aligned), lowest index on ties; bit-exact against torch.argmax on NaN-free input.  C <= 32.
+ * cabinet_predict_render -- visualize.py:50-61 and :165-177, byte for byte; all arrays but mean / std in device memory:
+ *   pred_rgb (N,H,W,3)    = palette (n_colors,3) [min(label, n_colors - 1)]                     1 <= n_colors <= 256
+ *   input_rgb (N,H,W,3)   = (uint8) (clip(image (N,3,H,W) * std[c] + mean[c], 0, 1) * 255)      or NULL: not written
+ *   overlay_rgb (N,H,W,3) = (uint8) ((float) in + alpha * (float) (colour - in))                or NULL: not written
+ *   in fp32, every product and sum rounded on its own (no fused multiply-add), truncated toward zero: numpy's float32
+ *   arithmetic and Pillow's Image.blend for 0 <= alpha <= 1.  image may be NULL when both optional outputs are;
+ *   mean and std point to three HOST floats each, read during the call.
+ * ------------------------------------------------------------------------- */
+int cabinet_predict_up_argmax_supported(int C, int hl, int wl, int H, int W);
+int cabinet_predict_up_argmax(const float* logits_low, int N, int C, int hl, int wl, int H, int W, unsigned char* labels,
+                              cabinet_stream_t stream);
+int cabinet_predict_argmax(const float* total, int N, int C, int H, int W, unsigned char* labels, cabinet_stream_t stream);
+int cabinet_predict_render(const unsigned char* labels, const float* image, const unsigned char* palette, int n_colors,
+                           const float* mean, const float* std, float alpha, int N, int H, int W, unsigned char* pred_rgb,
+                           unsigned char* input_rgb, unsigned char* overlay_rgb, cabinet_stream_t stream);
+
+/* ------------------------------------------------------------------------- *
  * Weight and input gradient of the 3x3 stride-2 padding-1 bias-free convolutions (added under ABI v8): NCHW, no layout copy,
  *   dw (Co,Ci,3,3) = sum_{b,oy,ox} dy (B,Co,Ho,Wo)[.,oy,ox] (x) x (B,Ci,H,W)[., 2 oy - 1 + ky, 2 ox - 1 + kx]
  * with Ho = (H - 1) / 2 + 1, Wo = (W - 1) / 2 + 1.  Replaces the weight-gradient half of the autograd backward of
