@@ -49,5 +49,9 @@ hipError_t bn_bwd_tail_run(const float* part, int nt, const float* dy, const flo
                            const float* bias, const float* save_mean, const float* save_invstd, int B, int C, int P,
                            int act, int training, float* dx, float* dweight, float* dbias, float* coef,
                            hipStream_t stream);
+// reduce + stand-alone finalize only: dweight, dbias and, at *coef (inside ws), the [2][C] coefficients of the dx expression
+hipError_t bn_act_bwd_stats_run(const float* dy, const float* x, const float* weight, const float* bias,
+                                const float* save_mean, const float* save_invstd, int B, int C, int P, int act, int training,
+                                float* dweight, float* dbias, void* ws, const float** coef, hipStream_t stream);
 
 }  // namespace cabinet

@@ -558,6 +558,23 @@ hipError_t bn_act_bwd_run(const float* dy, const float* x, const float* weight, 
                            dbias, coef, stream);
 }
 
+// The backward without its dx pass, for a consumer that forms dx itself while it stages its operand (K9's weight gradient, the
+// only reader of sb.conv1's dz): reduce + the stand-alone finalize, which writes dweight, dbias and -- at *coef, inside `ws`
+// (bn_act_workspace) -- (mean(du), mean(du * xhat)) per channel, the bits bn_bwd_tail_run's prologue plan gives its dx pass.
+hipError_t bn_act_bwd_stats_run(const float* dy, const float* x, const float* weight, const float* bias,
+                                const float* save_mean, const float* save_invstd, int B, int C, int P, int act, int training,
+                                float* dweight, float* dbias, void* ws, const float** coef, hipStream_t stream) {
+    const int chunks = ba_chunks(P), grid = B * C * chunks, nt = B * chunks;
+    float* part = static_cast<float*>(ws);
+    float* cf = reinterpret_cast<float*>(static_cast<char*>(ws) + align_up((size_t)2 * C * nt * sizeof(float), 256));
+    hipLaunchKernelGGL(bn_act_bwd_reduce_kernel, dim3(grid), dim3(BA_T), 0, stream, dy, x, save_mean, save_invstd, weight,
+                       bias, B, C, P, chunks, act, part);
+    hipLaunchKernelGGL(bn_act_bwd_finalize_kernel, dim3(C), dim3(BA_T), 0, stream, part, nt, C, (double)B * (double)P, training,
+                       dweight, dbias, cf);
+    *coef = cf;
+    return hipGetLastError();
+}
+
 size_t gate_act_workspace(int rows, int P) { return align_up((size_t)rows * ba_chunks(P) * sizeof(float), 256); }
 
 hipError_t gate_act_fwd_run(const float* x, const float* gate, int rows, int P, int act, float* y, hipStream_t stream) {

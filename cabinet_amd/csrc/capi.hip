@@ -118,6 +118,10 @@ hipError_t bn_dwconv_bwd_run(const float* dy, const float* z, const float* bn_w,
 // stem_conv.hip
 size_t stem_conv_wrw_workspace(int B, int H, int W);
 hipError_t stem_conv_fwd_run(const float* x, const float* w, int B, int H, int W, float* y, hipStream_t stream);
+size_t stem_conv_bn_bwd_workspace(int B, int H, int W);
+hipError_t stem_conv_bn_bwd_run(const float* g, const float* z, const float* x, const float* bn_weight, const float* bn_bias,
+                                const float* save_mean, const float* save_invstd, int B, int H, int W, int training, float* dw,
+                                float* dbn_weight, float* dbn_bias, void* ws, hipStream_t stream);
 hipError_t stem_conv_wrw_run(const float* dy, const float* x, int B, int H, int W, float* dw, void* ws,
                              hipStream_t stream);
 // pwconv_wide.hip
@@ -1157,19 +1161,46 @@ int cabinet_stem_conv_fwd(const float* x, const float* weight, int B, int H, int
                       "stem_conv_fwd launch");
 }
 
+// the weight-gradient kernel addresses one image's operands with 32-bit byte offsets: 64 Ho Wo floats (and 3 H W) below 4 GiB
+static int check_stem_wrw(int B, int H, int W, const char* who) {
+    if (int rc = check_stem(B, H, W, who)) return rc;
+    if ((long long)((H + 1) / 2) * ((W + 1) / 2) > (1LL << 24)) return fail(CABINET_ERR_UNSUPPORTED, "%s: plane too large", who);
+    return CABINET_OK;
+}
+
 size_t cabinet_stem_conv_wrw_workspace_bytes(int B, int H, int W) {
     return B > 0 && H > 0 && W > 0 ? cabinet::stem_conv_wrw_workspace(B, H, W) : 0;
 }
 
 int cabinet_stem_conv_wrw(const float* dy, const float* x, int B, int H, int W, float* dw, void* workspace,
                           size_t workspace_bytes, cabinet_stream_t stream) {
-    if (int rc = check_stem(B, H, W, "stem_conv_wrw")) return rc;
+    if (int rc = check_stem_wrw(B, H, W, "stem_conv_wrw")) return rc;
     if (!dy || !x || !dw) return fail(CABINET_ERR_INVALID_ARG, "stem_conv_wrw: null tensor pointer");
     const size_t need = cabinet::stem_conv_wrw_workspace(B, H, W);
     if (!workspace || workspace_bytes < need)
         return fail(CABINET_ERR_WORKSPACE, "stem_conv_wrw: workspace %zu < %zu bytes", workspace_bytes, need);
     return hip_status(cabinet::stem_conv_wrw_run(dy, x, B, H, W, dw, workspace, static_cast<hipStream_t>(stream)),
                       "stem_conv_wrw launch");
+}
+
+size_t cabinet_stem_conv_bn_bwd_workspace_bytes(int B, int H, int W) {
+    return B > 0 && H > 0 && W > 0 ? cabinet::stem_conv_bn_bwd_workspace(B, H, W) : 0;
+}
+
+int cabinet_stem_conv_bn_bwd(const float* g, const float* z, const float* x, const float* bn_weight, const float* bn_bias,
+                             const float* save_mean, const float* save_invstd, int B, int H, int W, int training, float* dw,
+                             float* dbn_weight, float* dbn_bias, void* workspace, size_t workspace_bytes,
+                             cabinet_stream_t stream) {
+    if (int rc = check_stem_wrw(B, H, W, "stem_conv_bn_bwd")) return rc;
+    if (!g || !z || !x || !bn_weight || !bn_bias || !save_mean || !save_invstd || !dw || !dbn_weight || !dbn_bias)
+        return fail(CABINET_ERR_INVALID_ARG, "stem_conv_bn_bwd: null tensor pointer");
+    CABINET_REQUIRE_ALIGNED("stem_conv_bn_bwd", g, z);
+    const size_t need = cabinet::stem_conv_bn_bwd_workspace(B, H, W);
+    if (!workspace || workspace_bytes < need)
+        return fail(CABINET_ERR_WORKSPACE, "stem_conv_bn_bwd: workspace %zu < %zu bytes", workspace_bytes, need);
+    return hip_status(cabinet::stem_conv_bn_bwd_run(g, z, x, bn_weight, bn_bias, save_mean, save_invstd, B, H, W, training, dw,
+                                                    dbn_weight, dbn_bias, workspace, static_cast<hipStream_t>(stream)),
+                      "stem_conv_bn_bwd launch");
 }
 
 // ------------------------------------------------------ thin pointwise convolution

@@ -15,6 +15,21 @@
 //   wrw : dW[co][k]  = sum_px dy[co][px] * patch[k][px]         A = dy tile (LDS, stride 129), B = patch gather,
 //         contraction over pixels; each wave accumulates the full 64 x 160 tile over its pixels, one ordered slab per
 //         workgroup, final ordered slab sum (slab_sum.hpp; no atomics).
+//
+// The weight gradient is one software-pipelined kernel with two operand forms.  Plain: A is dy.  BN (cabinet_stem_conv_bn_bwd, the
+// backward of relu(bn(conv(image)))): A is the BatchNorm + ReLU input gradient, formed per element from (g, z) and the six
+// per-channel scalars on the way into LDS with the expressions of bn_act_bwd_dx_kernel -- the same bits, so dW is the bits of
+// the pair bn_act_bwd + stem_conv_wrw, and the 537 MB dz of the config-3 step (one writer, one reader) is never written.
+// Staging: every load is unconditional (addresses clamped into the tensor, what lies outside replaced by 0 on the way into LDS
+// -- in the BN form the 0 is staged, not the dz of clamped operands), patch rows load as row segments at wave-uniform scalar
+// offsets with lane = column, and the operands of tile t+1 are requested before tile t is multiplied.  The staging this replaces
+// had each of its ~19 loads per thread and tile behind a bounds branch, hence one exposed memory latency each: the kernel
+// waited (SQ_WAIT_ANY 0.49 of wave cycles) at 0.42 of the fp32 MFMA rate.
+// Register budget at 2 workgroups per CU (256 VGPRs per wave, accumulators included): 160 accumulators; prefetch of the plain
+// form 32 (dy) + 11 (patch) = 240 VGPRs in all; the BN form prefetches half of the tile's channel groups (16 g + 16 z + 11) and
+// requests the other half, in two batches, once the first is in LDS: 255 VGPRs.  No scratch in any instantiation (the full
+// 64-register prefetch of the BN form spills; one workgroup per CU would hold it but leaves the MFMA pipe to a single wave).
+#include "act.hpp"
 #include "common.hpp"
 #include "slab_sum.hpp"
 
@@ -109,13 +124,39 @@ constexpr int SW_IW = (SW_TW - 1) * ST_S + ST_K;             // 69
 constexpr int SW_PATCH = ST_CI * SW_IH * SW_IW;              // 2691 floats
 constexpr int SW_DLD = SW_TH * SW_TW + 1;                    // 129: row stride of the dy tile
 constexpr int SW_KB = 5;                                     // 5 x 32 = 160 >= 147 columns
+constexpr int SW_G = ST_CO * SW_TH * (SW_TW / 4) / 256;      // 8: 4-pixel groups of the dy tile per thread (channels gco + 8 j)
+constexpr int SW_ROWS = ST_CI * SW_IH;                       // 39 patch rows of 69 columns: lane = column, 64..68 apart
+constexpr int SW_PR = (SW_ROWS + 3) / 4;                     // 10 patch rows per wave
+constexpr int SW_EXTRA = SW_ROWS * (SW_IW - 64);             // 195 elements in columns 64..68: one per thread
+constexpr int SW_BNP = 8;                                    // per-channel scalars of the BN form in LDS (7 used)
 
-__global__ __launch_bounds__(256, 2) void stem_conv_wrw_kernel(const float* __restrict__ dy, const float* __restrict__ x,
-                                                             StemShape s, int tiles_x, float* __restrict__ slabs) {
+// BN form of the "dy" operand: the BatchNorm + ReLU that follows the convolution, differentiated while the tile is staged
+//   dy = (gam * inv) * (du - m1 - xh * m2),  xh = (z - mu) * inv,  du = g * relu'(fmaf(xh, gam, bet))
+// (the expressions of bn_act_bwd_dx_kernel, bn_act.hip; coef = [m1 | m2] from bn_act_bwd_finalize_kernel)
+struct StemBn {
+    const float *z, *mean, *invstd, *weight, *bias, *coef;
+};
+
+// load at a wave-uniform base + a 32-bit per-lane byte offset (one address register per lane, whatever the number of bases)
+template <typename T>
+__device__ __forceinline__ T sw_ld(const float* base, unsigned byte_off) {
+    return *reinterpret_cast<const T*>(reinterpret_cast<const char*>(base) + byte_off);
+}
+
+// One kernel, two operand forms: BN = false reads dy; BN = true reads (g, z) and forms dy per element on the way into LDS, so
+// the 537 MB dz of sb.conv1's BatchNorm is never written.  VEC (Wo % 4 == 0, 16-byte aligned operands): 128-bit row loads.
+// Software pipeline: the operands of tile t+1 (PJ of the SW_G channel groups of g [and z], the image patch) are requested
+// before tile t is multiplied and written to LDS behind it; groups PJ..SW_G-1 are requested, in two batches, when the first
+// ones have been written (each batch waits one memory latency, which the other workgroup of the CU covers with its MFMAs).  No
+// load sits behind a branch: addresses are clamped into the tensor and what lies outside is replaced by 0 on the way into LDS.
+template <bool BN, bool VEC, int PJ>
+__global__ __launch_bounds__(256, 2) void stem_conv_wrw_kernel(const float* __restrict__ dy, const float* __restrict__ x, StemBn bn,
+                                                                StemShape s, int tiles_x, float* __restrict__ slabs) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     float* dys = smem;                          // [64][129]
     float* xs = dys + ST_CO * SW_DLD;           // [3][13][69]
-    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, li = lane & 31, h = lane >> 5;
+    float* bnp = xs + SW_PATCH;                 // [64][SW_BNP] (BN only)
+    const int tid = threadIdx.x, wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63, li = lane & 31, h = lane >> 5;
     const int strips_y = (s.Ho + SW_TH - 1) / SW_TH;
     const int b = blockIdx.x / strips_y, oy0 = (blockIdx.x - b * strips_y) * SW_TH;
     int ko[SW_KB];  // patch offset of this lane's column k = 32*kb + li (columns >= 147 read offset 0 and are dropped)
@@ -134,40 +175,127 @@ __global__ __launch_bounds__(256, 2) void stem_conv_wrw_kernel(const float* __re
             for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
     const float* xb = x + (size_t)b * ST_CI * s.H * s.W;
     const float* dyb = dy + (size_t)b * ST_CO * s.Ho * s.Wo;
+    const float* zb = BN ? bn.z + (size_t)b * ST_CO * s.Ho * s.Wo : nullptr;
     const int iy0 = oy0 * ST_S - ST_PAD;
-    for (int t = 0; t < tiles_x; ++t) {
-        const int ox0 = t * SW_TW, ix0 = ox0 * ST_S - ST_PAD;
-        __syncthreads();
-        for (int i = tid; i < SW_PATCH; i += 256) {
-            const int ci = i / (SW_IH * SW_IW), r = i - ci * SW_IH * SW_IW, yy = r / SW_IW, xx = r - yy * SW_IW;
-            const int iy = iy0 + yy, ix = ix0 + xx;
-            xs[i] = (iy >= 0 && iy < s.H && ix >= 0 && ix < s.W) ? xb[((size_t)ci * s.H + iy) * s.W + ix] : 0.f;
-        }
-        if ((s.Wo & 3) == 0 && ox0 + SW_TW <= s.Wo) {  // full-width tile: 128-bit row loads
-            for (int i = tid; i < ST_CO * SW_TH * (SW_TW / 4); i += 256) {
-                const int co = i / (SW_TH * (SW_TW / 4)), q = i - co * (SW_TH * (SW_TW / 4)), r = q / (SW_TW / 4),
-                          c = (q - r * (SW_TW / 4)) * 4;
-                const int oy = oy0 + r;
-                f32x4 v = {0.f, 0.f, 0.f, 0.f};
-                if (oy < s.Ho) v = *reinterpret_cast<const f32x4*>(dyb + ((size_t)co * s.Ho + oy) * s.Wo + ox0 + c);
-                float* d = dys + co * SW_DLD + r * SW_TW + c;
-                d[0] = v[0], d[1] = v[1], d[2] = v[2], d[3] = v[3];
+    if (BN && tid < ST_CO) {  // visible after the first barrier of the tile loop
+        const float mu = bn.mean[tid], inv = bn.invstd[tid], gam = bn.weight[tid];
+        float* q = bnp + tid * SW_BNP;
+        q[0] = mu, q[1] = inv, q[2] = gam, q[3] = bn.bias[tid], q[4] = bn.coef[tid], q[5] = bn.coef[ST_CO + tid], q[6] = gam * inv;
+    }
+    // dy tile: this thread's 4 pixels (row gr, columns gc..gc+3) of channels gco + 8 j
+    const int gco = tid >> 5, gr = (tid >> 3) & 3, gc = (tid & 7) * 4;
+    const bool grow_ok = oy0 + gr < s.Ho;
+    const size_t gcs = (size_t)8 * s.Ho * s.Wo;
+    const unsigned grow = ((unsigned)gco * s.Ho + min(oy0 + gr, s.Ho - 1)) * s.Wo;  // byte offsets fit 32 bits: the host's check
+    float* gdst = dys + gco * SW_DLD + gr * SW_TW + gc;
+    // patch: row SW_PR * wave + jj of the 39 (wave-uniform image offset, -1 above / below the image), column = lane ...
+    int prow[SW_PR];
+#pragma unroll
+    for (int jj = 0; jj < SW_PR; ++jj) {
+        const int rr = min(SW_PR * wave + jj, SW_ROWS - 1), ci = rr / SW_IH, iy = iy0 + rr - ci * SW_IH;
+        prow[jj] = __builtin_amdgcn_readfirstlane((iy >= 0 && iy < s.H) ? (ci * s.H + iy) * s.W : -1);  // a scalar register each
+    }
+    // ... and element `tid` of the 195 in columns 64..68.  Its indices are derived again from the thread id where they are used:
+    // carried through the tile loop they cost three registers of a budget that has none to spare.
+    struct Extra {
+        int lds, col, row;  // index in xs, patch column, image offset of the row (-1 outside)
+    };
+    auto extra = [&]() {
+        int te = tid;
+        asm volatile("" : "+v"(te));
+        const int i = min(te, SW_EXTRA - 1), er = i / (SW_IW - 64), ec = 64 + i - er * (SW_IW - 64);
+        const int eci = er / SW_IH, eiy = iy0 + er - eci * SW_IH;
+        return Extra{er * SW_IW + ec, ec, (eiy >= 0 && eiy < s.H) ? (eci * s.H + eiy) * s.W : -1};
+    };
+
+    f32x4 pg[SW_G], pz[SW_G];
+    float pp[SW_PR + 1];
+    auto request_dy = [&](int t, int j0, int j1) {
+        const int ox = t * SW_TW + gc;
+        if (VEC) {
+            const unsigned o = (grow + min(ox, s.Wo - 4)) * 4u;  // per lane; the channel group's base is wave-uniform
+#pragma unroll
+            for (int j = j0; j < j1; ++j) {
+                pg[j] = sw_ld<f32x4>(dyb + j * gcs, o);
+                if (BN) pz[j] = sw_ld<f32x4>(zb + j * gcs, o);
             }
         } else {
-            for (int i = tid; i < ST_CO * SW_TH * SW_TW; i += 256) {
-                const int co = i / (SW_TH * SW_TW), p = i - co * (SW_TH * SW_TW), r = p / SW_TW, c = p - r * SW_TW;
-                const int oy = oy0 + r, ox = ox0 + c;
-                dys[co * SW_DLD + p] = (oy < s.Ho && ox < s.Wo) ? dyb[((size_t)co * s.Ho + oy) * s.Wo + ox] : 0.f;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const unsigned o = (grow + min(ox + e, s.Wo - 1)) * 4u;
+#pragma unroll
+                for (int j = j0; j < j1; ++j) {
+                    pg[j][e] = sw_ld<float>(dyb + j * gcs, o);
+                    if (BN) pz[j][e] = sw_ld<float>(zb + j * gcs, o);
+                }
             }
         }
+    };
+    auto commit_dy = [&](int t, int j0, int j1) {
+        const int ox = t * SW_TW + gc;
+#pragma unroll
+        for (int j = j0; j < j1; ++j) {
+            f32x4 v = pg[j];
+            if (BN) {
+                const float* q = bnp + (gco + 8 * j) * SW_BNP;
+                const float mu = q[0], inv = q[1], gam = q[2], bet = q[3], m1 = q[4], m2 = q[5], gi = q[6];
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    const float xh = (pz[j][e] - mu) * inv;
+                    const float du = v[e] * act_grad(fmaf(xh, gam, bet), ACT_RELU);
+                    v[e] = gi * (du - m1 - xh * m2);
+                }
+            }
+#pragma unroll
+            for (int e = 0; e < 4; ++e)  // past Ho / Wo: 0, not the dz of a clamped load
+                gdst[j * 8 * SW_DLD + e] = (grow_ok && ox + e < s.Wo) ? v[e] : 0.f;
+            if (BN) __builtin_amdgcn_sched_barrier(0);  // one channel's 7 scalars in registers at a time, not all SW_G x 7
+        }
+    };
+    auto request_patch = [&](int t) {
+        const int ix0 = t * SW_TW * ST_S - ST_PAD;
+        const unsigned ixc = min(max(ix0 + lane, 0), s.W - 1) * 4u;
+#pragma unroll
+        for (int jj = 0; jj < SW_PR; ++jj) pp[jj] = sw_ld<float>(xb + max(prow[jj], 0), ixc);
+        const Extra x5 = extra();
+        pp[SW_PR] = sw_ld<float>(xb, (max(x5.row, 0) + min(max(ix0 + x5.col, 0), s.W - 1)) * 4u);
+    };
+    auto commit_patch = [&](int t) {
+        const int ix0 = t * SW_TW * ST_S - ST_PAD;
+        const bool okx = ix0 + lane >= 0 && ix0 + lane < s.W;
+#pragma unroll
+        for (int jj = 0; jj < SW_PR; ++jj)  // wave 3's tenth row is its ninth again: the same value to the same place
+            xs[min(SW_PR * wave + jj, SW_ROWS - 1) * SW_IW + lane] = (prow[jj] >= 0 && okx) ? pp[jj] : 0.f;
+        const Extra x5 = extra();
+        if (tid < SW_EXTRA) xs[x5.lds] = (x5.row >= 0 && ix0 + x5.col >= 0 && ix0 + x5.col < s.W) ? pp[SW_PR] : 0.f;
+    };
+
+    request_dy(0, 0, PJ);
+    request_patch(0);
+    for (int t = 0; t < tiles_x; ++t) {
+        __syncthreads();  // the previous tile's readers are done with dys / xs
+        commit_patch(t);
+        commit_dy(t, 0, PJ);
+        if (PJ < SW_G) {
+            __builtin_amdgcn_sched_barrier(0);  // the late groups' registers are the prefetched groups' registers: not both at once
+            request_dy(t, PJ, PJ + 2);
+            commit_dy(t, PJ, PJ + 2);
+            __builtin_amdgcn_sched_barrier(0);
+            request_dy(t, PJ + 2, SW_G);
+            commit_dy(t, PJ + 2, SW_G);
+        }
         __syncthreads();
+        if (t + 1 < tiles_x) {  // in flight underneath this tile's MFMAs
+            request_dy(t + 1, 0, PJ);
+            request_patch(t + 1);
+        }
         // this wave contracts over pixels p = 32*wave .. +31 (output row `wave` of the tile), two per MFMA
         const float* drow = dys + li * SW_DLD + 32 * wave + h;
-        const int prow = (ST_S * wave) * SW_IW;
+        const int prow0 = (ST_S * wave) * SW_IW;
 #pragma unroll 2
         for (int c0 = 0; c0 < 32; c0 += 2) {
             const float a0 = drow[c0], a1 = drow[32 * SW_DLD + c0];
-            const int poff = prow + ST_S * (c0 + h);
+            const int poff = prow0 + ST_S * (c0 + h);
 #pragma unroll
             for (int kb = 0; kb < SW_KB; ++kb) {
                 const float bv = xs[ko[kb] + poff];
@@ -180,6 +308,9 @@ __global__ __launch_bounds__(256, 2) void stem_conv_wrw_kernel(const float* __re
     __syncthreads();
     float* red = smem;  // [64][161] reused (fits: 64*161 <= 64*129 + 2691)
     constexpr int RLD = 161;
+    int tid_e = tid;
+    asm volatile("" : "+v"(tid_e));  // the addresses below are formed here, not carried in registers through the tile loop
+    const int li_e = tid_e & 31, h_e = (tid_e >> 5) & 1;
     for (int w = 0; w < 4; ++w) {
         if (wave == w) {
 #pragma unroll
@@ -188,7 +319,7 @@ __global__ __launch_bounds__(256, 2) void stem_conv_wrw_kernel(const float* __re
                 for (int kb = 0; kb < SW_KB; ++kb)
 #pragma unroll
                     for (int r = 0; r < 16; ++r) {
-                        const int co = 32 * i + acc_row(r) + 4 * h, k = 32 * kb + li;
+                        const int co = 32 * i + acc_row(r) + 4 * h_e, k = 32 * kb + li_e;
                         float* p = red + co * RLD + k;
                         *p = (w == 0) ? acc[i][kb][r] : *p + acc[i][kb][r];
                     }
@@ -196,7 +327,7 @@ __global__ __launch_bounds__(256, 2) void stem_conv_wrw_kernel(const float* __re
         __syncthreads();
     }
     float* slab = slabs + (size_t)blockIdx.x * ST_CO * ST_KK;
-    for (int i = tid; i < ST_CO * ST_KK; i += 256) {
+    for (int i = tid_e; i < ST_CO * ST_KK; i += 256) {
         const int co = i / ST_KK, k = i - co * ST_KK;
         slab[i] = red[co * RLD + k];
     }
@@ -226,18 +357,51 @@ hipError_t stem_conv_fwd_run(const float* x, const float* w, int B, int H, int W
     return hipGetLastError();
 }
 
-hipError_t stem_conv_wrw_run(const float* dy, const float* x, int B, int H, int W, float* dw, void* ws,
-                             hipStream_t stream) {
+// prefetch depth of the two forms (of SW_G channel groups): see the register budget in the header comment
+constexpr int SW_PJ_PLAIN = 8, SW_PJ_BN = 4, SW_PJ_BN_RAGGED = 2;
+
+template <bool BN>
+static hipError_t stem_wrw_launch(const float* dy, const float* x, const StemBn& bn, int B, int H, int W, float* dw, float* slabs,
+                                  hipStream_t stream) {
     const StemShape s = stem_shape(B, H, W);
-    const int nslab = B * ceil_div(s.Ho, SW_TH);
-    const size_t lds = ((size_t)ST_CO * SW_DLD + SW_PATCH) * sizeof(float);
-    float* slabs = static_cast<float*>(ws);
-    hipLaunchKernelGGL(stem_conv_wrw_kernel, dim3(nslab), dim3(256), lds, stream, dy, x, s, ceil_div(s.Wo, SW_TW), slabs);
+    const int nslab = B * ceil_div(s.Ho, SW_TH), tiles_x = ceil_div(s.Wo, SW_TW);
+    const size_t lds = ((size_t)ST_CO * SW_DLD + SW_PATCH + (BN ? ST_CO * SW_BNP : 0)) * sizeof(float);
+    constexpr int PJ = BN ? SW_PJ_BN : SW_PJ_PLAIN, PJR = BN ? SW_PJ_BN_RAGGED : SW_PJ_PLAIN;
+    const bool vec = (s.Wo & 3) == 0 && ((reinterpret_cast<uintptr_t>(dy) | reinterpret_cast<uintptr_t>(bn.z)) & 15) == 0;
+    if (vec)
+        hipLaunchKernelGGL((stem_conv_wrw_kernel<BN, true, PJ>), dim3(nslab), dim3(256), lds, stream, dy, x, bn, s, tiles_x, slabs);
+    else
+        hipLaunchKernelGGL((stem_conv_wrw_kernel<BN, false, PJR>), dim3(nslab), dim3(256), lds, stream, dy, x, bn, s, tiles_x, slabs);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
     // the slabs (1024 x 38 KB at 8 x 1024^2) summed on the whole chip: 32 slab lanes per 128-byte segment, then in order
     slab_sum_launch(slabs, nslab, ST_CO * ST_KK, dw, stream);
     return hipGetLastError();
+}
+
+hipError_t stem_conv_wrw_run(const float* dy, const float* x, int B, int H, int W, float* dw, void* ws,
+                             hipStream_t stream) {
+    return stem_wrw_launch<false>(dy, x, StemBn{}, B, H, W, dw, static_cast<float*>(ws), stream);
+}
+
+// workspace: the BatchNorm partials + coef (bn_act_workspace), then the slabs
+size_t stem_conv_bn_bwd_workspace(int B, int H, int W) {
+    const StemShape s = stem_shape(B, H, W);
+    return bn_act_workspace(B, ST_CO, s.Ho * s.Wo) + stem_conv_wrw_workspace(B, H, W);
+}
+
+// backward of relu(bn(stem_conv(image))) as one operator: g = dL/dy, z = the convolution's output.  BatchNorm's reduce and
+// finalize (dweight, dbias, coef), then the weight gradient with dz formed in its loader.
+hipError_t stem_conv_bn_bwd_run(const float* g, const float* z, const float* x, const float* bn_weight, const float* bn_bias,
+                                const float* save_mean, const float* save_invstd, int B, int H, int W, int training, float* dw,
+                                float* dbn_weight, float* dbn_bias, void* ws, hipStream_t stream) {
+    const StemShape s = stem_shape(B, H, W);
+    const float* coef = nullptr;
+    hipError_t e = bn_act_bwd_stats_run(g, z, bn_weight, bn_bias, save_mean, save_invstd, B, ST_CO, s.Ho * s.Wo, ACT_RELU, training,
+                                        dbn_weight, dbn_bias, ws, &coef, stream);
+    if (e != hipSuccess) return e;
+    float* slabs = reinterpret_cast<float*>(static_cast<char*>(ws) + bn_act_workspace(B, ST_CO, s.Ho * s.Wo));
+    return stem_wrw_launch<true>(g, x, StemBn{z, save_mean, save_invstd, bn_weight, bn_bias, coef}, B, H, W, dw, slabs, stream);
 }
 
 }  // namespace cabinet

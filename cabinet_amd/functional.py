@@ -9,6 +9,7 @@
 ``bn_relu_cls``     cabinet.py:90-92, :161-172 (BN -> ReLU -> 1x1 classifier)  (K12)   ``conv3x3``  cabinet.py:59, :88-89, :160 (K11)
 ``dwconv`` / ``bn_act_dwconv``   mobilenetv3.py:118-126,135-143           (K8)
 ``stem_conv``       cabinet.py:111                                        (K9)     ``pwconv``   mobilenetv3.py:128-131
+``stem_conv_bn_relu``  cabinet.py:111 + :42-44 (the stem's conv -> BN -> ReLU as one node: K9 + K7, no BatchNorm dx pass)
 OHEM head           src/utils/loss.py:51-80 + cabinet.py:240-245          (``ohem_up_*``, used by cabinet_amd.loss)
 evaluation tail     src/scripts/evaluate.py:69-159, :193-226              (K13: ``eval_chip_accum`` / ``eval_scale_merge`` /
                     ``eval_argmax_hist``, no autograd; used by cabinet_amd.evaluate)
@@ -1568,6 +1569,66 @@ def stem_conv(x, conv):
     if not x.is_cuda:
         raise RuntimeError("stem_conv: device tensors only")
     return _StemConv.apply(x, conv.weight)
+
+
+# CABINET_STEM_BN_FUSED=0: the stem goes back to the two nodes bn_act(stem_conv(...)) -- same-box A/B timing and the equality tests
+STEM_BN_FUSED = _os.environ.get("CABINET_STEM_BN_FUSED", "1") != "0"
+
+
+class _StemConvBnRelu(torch.autograd.Function):
+    """relu(bn(stem_conv(image))) as one node: the forward is K9's and K7's, called in that order; the backward never writes the
+    BatchNorm's input gradient (B, 64, H/2, W/2) -- its only reader, the weight-gradient kernel, forms it while staging."""
+
+    @staticmethod
+    @torch.amp.custom_fwd(device_type="cuda", cast_inputs=torch.float32)
+    def forward(fn_ctx, x, weight, bn_weight, bn_bias, run_mean, run_var, training, momentum, eps):
+        lib = _lib.load()
+        x, w, bn_weight, bn_bias = _f32c(x), _f32c(weight), _f32c(bn_weight), _f32c(bn_bias)
+        B, _, H, W = x.shape
+        z = torch.empty((B, 64, (H - 1) // 2 + 1, (W - 1) // 2 + 1), dtype=torch.float32, device=x.device)
+        y = torch.empty_like(z)
+        mean = torch.empty(64, dtype=torch.float32, device=x.device)
+        invstd = torch.empty(64, dtype=torch.float32, device=x.device)
+        P = z.shape[2] * z.shape[3]
+        with torch.cuda.device(x.device):
+            rc = lib.cabinet_stem_conv_fwd(_ptr(x), _ptr(w), B, H, W, _ptr(z), _stream_handle(x.device))
+            _lib.check(rc, "cabinet_stem_conv_fwd")
+            ws, nbytes = _workspace(lib.cabinet_bn_act_workspace_bytes(B, 64, P), x.device)
+            rc = lib.cabinet_bn_act_fwd(_ptr(z), _ptr(bn_weight), _ptr(bn_bias), _ptr(run_mean), _ptr(run_var), None, B, 64, P,
+                                        _ACT_CODES["relu"], int(training), float(momentum), float(eps), _ptr(y), _ptr(mean),
+                                        _ptr(invstd), _ptr(ws), nbytes, _stream_handle(x.device))
+            _lib.check(rc, "cabinet_bn_act_fwd")
+        fn_ctx.save_for_backward(x, z, w, bn_weight, bn_bias, mean, invstd)
+        fn_ctx.training = bool(training)
+        return y
+
+    @staticmethod
+    @torch.amp.custom_bwd(device_type="cuda")
+    def backward(fn_ctx, g):
+        lib = _lib.load()
+        x, z, w, bn_weight, bn_bias, mean, invstd = fn_ctx.saved_tensors
+        g = _f32c(g)
+        B, _, H, W = x.shape
+        dw, dgam, dbet = torch.empty_like(w), torch.empty_like(bn_weight), torch.empty_like(bn_bias)
+        ws, nbytes = _workspace(lib.cabinet_stem_conv_bn_bwd_workspace_bytes(B, H, W), x.device)
+        with torch.cuda.device(x.device):
+            rc = lib.cabinet_stem_conv_bn_bwd(_ptr(g), _ptr(z), _ptr(x), _ptr(bn_weight), _ptr(bn_bias), _ptr(mean), _ptr(invstd),
+                                              B, H, W, int(fn_ctx.training), _ptr(dw), _ptr(dgam), _ptr(dbet), _ptr(ws), nbytes,
+                                              _stream_handle(x.device))
+        _lib.check(rc, "cabinet_stem_conv_bn_bwd")
+        return None, dw, dgam, dbet, None, None, None, None, None
+
+
+def stem_conv_bn_relu(x, conv, bn):
+    """``relu(bn(conv(x)))`` for the stem (see stem_conv_supported) on an image that needs no gradient: the values, the running
+    buffers and the three parameter gradients of ``bn_act(stem_conv(x, conv), bn, "relu")``, bit for bit, without the BatchNorm's
+    dx pass (reference cabinet.py:111 with :42-44)."""
+    if not x.is_cuda:
+        raise RuntimeError("stem_conv_bn_relu: device tensors only")
+    if x.requires_grad:
+        raise RuntimeError("stem_conv_bn_relu: the image gets no gradient here; use bn_act(stem_conv(...))")
+    training, momentum = _bn_step(bn)
+    return _StemConvBnRelu.apply(x, conv.weight, bn.weight, bn.bias, bn.running_mean, bn.running_var, training, momentum, bn.eps)
 
 
 # --------------------------------------------------------------------------- thin pointwise convolution (K10)

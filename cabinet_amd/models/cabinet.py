@@ -27,7 +27,7 @@ import torch.nn.functional as F
 from .. import functional as _functional
 from ..functional import (batched_bn_counters, bn_act, bn_relu_cls, conv1x1, conv1x1_bias_supported, conv3x3, conv3x3_bn_part,
                           conv3x3_supported, Conv2dS2, ffm_fused, ffm_fused_upsampled, pwconv_wide, pwconv_wide_supported, stem_conv,
-                          stem_conv_supported)
+                          stem_conv_bn_relu, stem_conv_supported)
 from .cab import ContextAggregationBlock
 from .constants import MODEL_CONFIG, MOBILENETV3_CFGS
 from .mobilenetv3 import MobileNetV3
@@ -89,6 +89,10 @@ class ConvBNReLU(nn.Module):
             return self.relu(self.bn(self.conv(x)))
         if x.shape[1] == 3 and stem_conv_supported(self.conv):
             # K9: the 7x7/2 image stem without NHWC round trips; K7: BatchNorm + ReLU in one streaming pass pair
+            if (_functional.STEM_BN_FUSED and torch.is_grad_enabled() and not x.requires_grad and self.conv.weight.requires_grad
+                    and self.bn.weight.requires_grad and self.bn.bias.requires_grad):
+                # training on an image: one node, whose backward forms the BatchNorm's dx inside the weight-gradient kernel
+                return stem_conv_bn_relu(x, self.conv, self.bn)
             return bn_act(stem_conv(x, self.conv), self.bn, "relu")
         return _conv3x3_bn_relu(self.conv, self.bn, x)  # K11 for conv_out's 256 -> 256 3x3 (cabinet.py:160)
 

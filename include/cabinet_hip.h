@@ -525,6 +525,22 @@ int cabinet_stem_conv_wrw(const float* dy, const float* x, int B, int H, int W, 
                           void* workspace, size_t workspace_bytes, cabinet_stream_t stream);
 
 /* ------------------------------------------------------------------------- *
+ * Backward of relu(bn(stem_conv(image))) as one operator: the stem's ConvBNReLU, src/models/cabinet.py:111 with the
+ * bn -> relu tail of ConvBNReLU.forward, cabinet.py:42-44.  g (B,64,Ho,Wo) is the gradient at the ReLU's output, z
+ * (B,64,Ho,Wo) the convolution's output, x (B,3,H,W) the image; save_mean / save_invstd (64) as cabinet_bn_act_fwd
+ * returned them.  BatchNorm's reduce + finalize give dbn_weight / dbn_bias (64); the weight-gradient kernel then forms the
+ * BatchNorm input gradient per element while it stages its tile, so that (B,64,Ho,Wo) tensor is never written.
+ * dw (64,3,7,7) and the BatchNorm gradients are bit for bit those of cabinet_bn_act_bwd followed by
+ * cabinet_stem_conv_wrw.  training = 0: eval-mode BatchNorm (save_mean / save_invstd from the running buffers).
+ * g, z 16-byte aligned.  Deterministic.
+ * ------------------------------------------------------------------------- */
+size_t cabinet_stem_conv_bn_bwd_workspace_bytes(int B, int H, int W);
+int cabinet_stem_conv_bn_bwd(const float* g, const float* z, const float* x, const float* bn_weight, const float* bn_bias,
+                             const float* save_mean, const float* save_invstd, int B, int H, int W, int training,
+                             float* dw, float* dbn_weight, float* dbn_bias,
+                             void* workspace, size_t workspace_bytes, cabinet_stream_t stream);
+
+/* ------------------------------------------------------------------------- *
  * Thin pointwise (1x1, bias-free, stride 1) convolution on large planes, streaming form:
  * y (B,Co,P) = W (Co,Ci) . x (B,Ci,P).  Replaces the nn.Conv2d(kernel_size=1) of the first MBConv blocks,
  * src/models/mobilenetv3.py:128-131,144-151, where the product is HBM-bound (Ci, Co <= 120).
