@@ -24,10 +24,16 @@
 // over the taps where both quotients are integers and in range: by the four parity classes of (iy, ix), which take 1, 2, 2 and
 // 4 taps, so no product with a structural zero is executed.  M = ci, N = the pixels of a class, K = co x taps, on the exact-fp32
 // MFMA 16x16x4: a wave owns 16 input channels and keeps their 64 x 9 weights in 144 registers for the whole kernel (the A
-// operand never touches the LDS); the workgroup stages two dy rows ([co][2][72]) per step and every wave reads its B operand
-// from them, tap by tap.  The even- and odd-column classes of one lane are neighbours in dX: a lane
+// operand never touches the LDS); the workgroup keeps a ring of three dy rows ([co][3][80]) in LDS -- rows m and m + 1 of the
+// step, row m + 2 requested before the step's MFMAs and written behind them, every row fetched once -- and every wave reads its B
+// operand from them, tap by tap.  Staging loads are unconditional row segments (clamped addresses, 0 selected on the way into
+// LDS).  The even- and odd-column classes of one lane are neighbours in dX: a lane
 // stores them as one pair, 16 lanes as one 128-byte run.  Every element of dX is written (rows and columns past the last tap
 // included: their sums are over zero-staged dy).
+// Register budget at 2 workgroups per CU (256 VGPRs): 144 weights, 16 accumulators, 8 tap partials, 17 prefetch, two half-taps of
+// B operands (16); no scratch.  The staging this replaces (both rows of a pair between two barriers, ~33 loads per thread each
+// behind two divisions and a bounds select, row m + 1 fetched twice) ran at 0.41 of the fp32 MFMA rate with 0.46 of the wave
+// cycles parked; this one at 0.73 with 0.11.
 #include "common.hpp"
 #include "slab_sum.hpp"
 
@@ -192,8 +198,15 @@ typedef float f32x4v __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ f32x4v mfma16(float a, float b, f32x4v c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
 
 constexpr int CD_NT = 64;             // columns n of dy per step: 128 columns of dX
-constexpr int CD_RP = 72;             // row pitch of the dy tile (65 columns live)
-constexpr int CD_CP = 2 * CD_RP;      // 144: channel pitch, = 16 mod 32 (the two channels of a 32-lane read group: disjoint banks)
+constexpr int CD_RP = 80;             // row pitch of the dy ring (65 columns live)
+constexpr int CD_SLOTS = 3;           // rows m, m + 1 of the step and row m + 2 on its way in
+constexpr int CD_CP = CD_SLOTS * CD_RP;  // 240: channel pitch, = 16 mod 32 (the two channels of a 32-lane read group: disjoint banks)
+constexpr int CD_PR = CW_C / 4;       // 16 channels' row segments per wave and dy row
+
+// load at a wave-uniform base + a 32-bit per-lane byte offset
+__device__ __forceinline__ float cd_ld(const float* base, unsigned byte_off) {
+    return *reinterpret_cast<const float*>(reinterpret_cast<const char*>(base) + byte_off);
+}
 
 // the tap of dY that input parity 0 (even) / 1 (odd) takes with kernel index k: even rows take k = 1 from row m; odd rows
 // take k = 0 from row m + 1 and k = 2 from row m
@@ -203,8 +216,8 @@ __host__ __device__ constexpr int cd_shift(int k) { return k == 0 ? 1 : 0; }
 __global__ __launch_bounds__(256, 2) void conv3x3s2_dgrad64_kernel(const float* __restrict__ dy, const float* __restrict__ w,
                                                                  C3Shape s, int tiles_n, int strips, int rows_per,
                                                                  float* __restrict__ dx) {
-    __shared__ __attribute__((aligned(16))) float dys[CW_C * CD_CP];  // [co][2 rows][72]
-    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, lc = lane & 15, lk = lane >> 4;
+    __shared__ __attribute__((aligned(16))) float dys[CW_C * CD_CP];  // [co][3 slots][80]: a ring of dy rows
+    const int tid = threadIdx.x, wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63, lc = lane & 15, lk = lane >> 4;
     int bi = blockIdx.x;
     const int tn = bi % tiles_n;
     bi /= tiles_n;
@@ -223,14 +236,42 @@ __global__ __launch_bounds__(256, 2) void conv3x3s2_dgrad64_kernel(const float* 
     float* dxb = dx + ((size_t)b * CW_C + ci0 + 4 * lk) * s.H * s.W;
     const float* brow = dys + lk * CD_CP + lc;
     const bool pair_ok = (s.W & 1) == 0;  // rows of dX start 8-byte aligned
+    // Staging of one dy row (64 channels x 65 columns): this wave's 16 channels as row segments (wave-uniform (co, row) base,
+    // lane = column n0 + lane) and, one per thread of wave 0, the halo column n0 + 64 of channel tid.  Every load is
+    // unconditional: row and column are clamped into the tensor and what lies outside is replaced by 0 on the way into LDS.
+    const unsigned colo = (unsigned)min(n0 + lane, s.Wo - 1) * 4u;
+    const bool col_ok = n0 + lane < s.Wo, halo_ok = n0 + CD_NT < s.Wo;
+    float pp[CD_PR + 1];
+    auto request = [&](int r) {
+        const int oy = min(r, s.Ho - 1);
+#pragma unroll
+        for (int j = 0; j < CD_PR; ++j) pp[j] = cd_ld(dyb + ((size_t)(CD_PR * wave + j) * s.Ho + oy) * s.Wo, colo);
+        int te = tid;  // the halo element's address is formed here, not carried (two registers) through the MFMAs
+        asm volatile("" : "+v"(te));
+        pp[CD_PR] = dyb[((size_t)min(te, CW_C - 1) * s.Ho + oy) * s.Wo + min(n0 + CD_NT, s.Wo - 1)];
+    };
+    auto commit = [&](int r, int slot) {
+        const bool row_ok = r < s.Ho;
+        float* d = dys + slot * CD_RP;
+#pragma unroll
+        for (int j = 0; j < CD_PR; ++j) d[(CD_PR * wave + j) * CD_CP + lane] = (row_ok && col_ok) ? pp[j] : 0.f;
+        if (tid < CW_C) d[tid * CD_CP + CD_NT] = (row_ok && halo_ok) ? pp[CD_PR] : 0.f;
+    };
+    // Row r of the strip lives in slot (r - m_begin) % 3.  Step m multiplies rows (m, m + 1) while row m + 2 is in flight; it is
+    // written at the top of step m + 1 over row m - 1, whose last readers (step m - 1) are behind the barrier of step m: one
+    // barrier per step, every dy row fetched once per workgroup.
+    request(m_begin);
+    commit(m_begin, 0);
+    request(m_begin + 1);
+    int s0 = 0;  // slot of row m
     for (int m = m_begin; m < m_end; ++m) {
-        __syncthreads();  // the previous row pair's operand reads are done
-        for (int i = tid; i < CW_C * 2 * (CD_NT + 1); i += 256) {
-            const int co = i / (2 * (CD_NT + 1)), r = i - co * 2 * (CD_NT + 1), rr = r / (CD_NT + 1), c = r - rr * (CD_NT + 1);
-            const int oy = m + rr, ox = n0 + c;
-            dys[co * CD_CP + rr * CD_RP + c] = (oy < s.Ho && ox < s.Wo) ? dyb[((size_t)co * s.Ho + oy) * s.Wo + ox] : 0.f;
-        }
+        const int s1 = s0 == CD_SLOTS - 1 ? 0 : s0 + 1;
+        commit(m + 1, s1);
         __syncthreads();
+        if (m + 1 < m_end) request(m + 2);  // in flight underneath this step's MFMAs
+        const float* bp0 = brow + s0 * CD_RP;  // row m
+        const float* bp1 = brow + s1 * CD_RP;  // row m + 1
+        s0 = s1;
 #pragma unroll 1  // 144 MFMAs per group already: unrolling the groups only spills the weights
         for (int ng = 0; ng < CD_NT / 16 && n0 + 16 * ng < s.Wo; ++ng) {
             f32x4v acc[2][2];
@@ -238,23 +279,34 @@ __global__ __launch_bounds__(256, 2) void conv3x3s2_dgrad64_kernel(const float* 
             for (int i = 0; i < 2; ++i)
 #pragma unroll
                 for (int j = 0; j < 2; ++j) acc[i][j] = f32x4v{0.f, 0.f, 0.f, 0.f};
-            const float* bp = brow + 16 * ng;
             // tap by tap, the 64 output channels of a tap as two interleaved chains of 32 (k-steps of 4 channels, even and odd:
             // no MFMA waits on the one before it), folded into the class sum in a fixed order: the longest fp32 chain is 32
             // terms, which keeps the result as close to fp64 as the stock kernel's
+            // The B operands of half-tap g + 1 (8 k-steps) are read while half-tap g is multiplied, and no further ahead (the
+            // scheduling barrier): with the 144 weights and the row in flight there are registers for two half-taps' operands,
+            // not for the taps the scheduler would hoist.
+            float bv[2][8];
+            auto read_half = [&](int g, float* v) {
+                const int t = g / 2;
+                const float* bt = (cd_shift(t / 3) ? bp1 : bp0) + 16 * ng + cd_shift(t % 3);
 #pragma unroll
-            for (int ky = 0; ky < 3; ++ky)
+                for (int i = 0; i < 8; ++i) v[i] = bt[4 * (8 * (g % 2) + i) * CD_CP];
+            };
+            read_half(0, bv[0]);
+            f32x4v p0, p1;
 #pragma unroll
-                for (int kx = 0; kx < 3; ++kx) {
-                    f32x4v p0 = {0.f, 0.f, 0.f, 0.f}, p1 = {0.f, 0.f, 0.f, 0.f};
-                    const float* bt = bp + cd_shift(ky) * CD_RP + cd_shift(kx);
+            for (int g = 0; g < 18; ++g) {
+                const int t = g / 2, k8 = 8 * (g % 2);
+                if (g + 1 < 18) read_half(g + 1, bv[(g + 1) & 1]);
+                if (g % 2 == 0) p0 = p1 = f32x4v{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-                    for (int ks = 0; ks < 16; ks += 2) {
-                        p0 = mfma16(wr[3 * ky + kx][ks], bt[4 * ks * CD_CP], p0);
-                        p1 = mfma16(wr[3 * ky + kx][ks + 1], bt[4 * (ks + 1) * CD_CP], p1);
-                    }
-                    acc[cd_par(ky)][cd_par(kx)] += p0 + p1;
+                for (int i = 0; i < 8; i += 2) {
+                    p0 = mfma16(wr[t][k8 + i], bv[g & 1][i], p0);
+                    p1 = mfma16(wr[t][k8 + i + 1], bv[g & 1][i + 1], p1);
                 }
+                if (g % 2 == 1) acc[cd_par(t / 3)][cd_par(t % 3)] += p0 + p1;
+                __builtin_amdgcn_sched_barrier(0);
+            }
             // column pair (2 n, 2 n + 1) of one lane: 16 lanes store 128 contiguous bytes of a dX row
             const int ix = 2 * (n0 + 16 * ng + lc);
 #pragma unroll

@@ -16,6 +16,12 @@
 //         contraction over pixels; each wave accumulates the full 64 x 160 tile over its pixels, one ordered slab per
 //         workgroup, final ordered slab sum (slab_sum.hpp; no atomics).
 //
+// The forward is software-pipelined over the tiles of its strip like the weight gradient below: the patch of tile t+1 is requested
+// (unconditional row-segment loads, clamped, 0 selected on the way into LDS: 16 rows per wave + 2 elements of columns 64..68 per
+// thread) before tile t's 296 MFMAs and written behind them.  135 VGPRs: store addresses and patch offsets are formed where they
+// are used, not hoisted over the tile loop (the staging this replaces -- 17 loads per thread and tile, each behind a division and
+// a bounds test -- ran at 0.50 of the fp32 MFMA rate with 0.34-0.40 of the wave cycles parked; this one at 0.72 with 0.12-0.14).
+//
 // The weight gradient is one software-pipelined kernel with two operand forms.  Plain: A is dy.  BN (cabinet_stem_conv_bn_bwd, the
 // backward of relu(bn(conv(image)))): A is the BatchNorm + ReLU input gradient, formed per element from (g, z) and the six
 // per-channel scalars on the way into LDS with the expressions of bn_act_bwd_dx_kernel -- the same bits, so dW is the bits of
@@ -49,37 +55,89 @@ struct StemShape {
     int B, H, W, Ho, Wo;
 };
 
+// load at a wave-uniform base + a 32-bit per-lane byte offset (one address register per lane, whatever the number of bases)
+template <typename T>
+__device__ __forceinline__ T sw_ld(const float* base, unsigned byte_off) {
+    return *reinterpret_cast<const T*>(reinterpret_cast<const char*>(base) + byte_off);
+}
+
 // ------------------------------------------------------------------------------------------------ forward
 constexpr int SF_TH = 8, SF_TW = 32;                         // output tile of a workgroup step
 constexpr int SF_IH = (SF_TH - 1) * ST_S + ST_K;             // 21
 constexpr int SF_IW = (SF_TW - 1) * ST_S + ST_K;             // 69
 constexpr int SF_PATCH = ST_CI * SF_IH * SF_IW;              // 4347 floats
+constexpr int SF_ROWS = ST_CI * SF_IH;                       // 63 patch rows of 69 columns: lane = column, 64..68 apart
+constexpr int SF_PR = (SF_ROWS + 3) / 4;                     // 16 patch rows per wave
+constexpr int SF_XW = SF_IW - 64;                            // the 5-column tail of a row
+constexpr int SF_EXTRA = SF_ROWS * SF_XW;                    // 315 tail elements: two per thread
+constexpr int SF_XT = (SF_EXTRA + 255) / 256;                // 2
+constexpr int SF_KG = 2, SF_NG = ST_KP / (2 * SF_KG);        // 37 groups of two k-steps (8 MFMAs) in the operand pipeline
+static_assert(SF_NG * 2 * SF_KG == ST_KP, "k-groups tile the contraction");
 
-__global__ __launch_bounds__(256) void stem_conv_fwd_kernel(const float* __restrict__ x, const float* __restrict__ wgt,
-                                                             StemShape s, int tiles_x, float* __restrict__ y) {
+// Software pipeline over the tiles of a strip: the patch of tile t+1 is requested (unconditional loads: addresses clamped into
+// the image, what lies outside replaced by 0 on the way into LDS) before tile t is multiplied, and written into the one patch
+// buffer behind the MFMAs and a barrier.
+__global__ __launch_bounds__(256, 2) void stem_conv_fwd_kernel(const float* __restrict__ x, const float* __restrict__ wgt,
+                                                                StemShape s, int tiles_x, float* __restrict__ y) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     float* wl = smem;                          // [64][149]
     float* xs = wl + ST_CO * ST_WLD;           // [3][21][69]
-    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, li = lane & 31, h = lane >> 5;
+    const int tid = threadIdx.x, wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63, li = lane & 31, h = lane >> 5;
     const int strips_y = (s.Ho + SF_TH - 1) / SF_TH;
     const int b = blockIdx.x / strips_y, oy0 = (blockIdx.x - b * strips_y) * SF_TH;
+    const float* xb = x + (size_t)b * ST_CI * s.H * s.W;
+    const int iy0 = oy0 * ST_S - ST_PAD;
+    // patch: row SF_PR * wave + jj of the 63 (wave-uniform image row ci * H + iy, -1 above / below the image), column = lane ...
+    int prow[SF_PR];
+#pragma unroll
+    for (int jj = 0; jj < SF_PR; ++jj) {
+        const int rr = min(SF_PR * wave + jj, SF_ROWS - 1), ci = rr / SF_IH, iy = iy0 + rr - ci * SF_IH;
+        prow[jj] = __builtin_amdgcn_readfirstlane((iy >= 0 && iy < s.H) ? ci * s.H + iy : -1);  // a scalar register each
+    }
+    // ... and elements tid, tid + 256 of the 315 in columns 64..68
+    int xlds[SF_XT], xcol[SF_XT], xrow[SF_XT];  // index in the patch, patch column, image row (-1 outside)
+#pragma unroll
+    for (int e = 0; e < SF_XT; ++e) {
+        const int i = min(tid + 256 * e, SF_EXTRA - 1), er = i / SF_XW, ci = er / SF_IH, iy = iy0 + er - ci * SF_IH;
+        xcol[e] = 64 + i - er * SF_XW;
+        xlds[e] = er * SF_IW + xcol[e];
+        xrow[e] = (iy >= 0 && iy < s.H) ? ci * s.H + iy : -1;
+    }
+    float pp[SF_PR + SF_XT];
+    auto request = [&](int t) {
+        const int ix0 = t * SF_TW * ST_S - ST_PAD;
+        const unsigned ixc = min(max(ix0 + lane, 0), s.W - 1) * 4u;
+#pragma unroll
+        for (int jj = 0; jj < SF_PR; ++jj) pp[jj] = sw_ld<float>(xb + (size_t)max(prow[jj], 0) * s.W, ixc);
+#pragma unroll
+        for (int e = 0; e < SF_XT; ++e)
+            pp[SF_PR + e] = xb[(size_t)max(xrow[e], 0) * s.W + min(max(ix0 + xcol[e], 0), s.W - 1)];
+    };
+    auto commit = [&](int t) {
+        const int ix0 = t * SF_TW * ST_S - ST_PAD;
+        const bool okx = ix0 + lane >= 0 && ix0 + lane < s.W;
+#pragma unroll
+        for (int jj = 0; jj < SF_PR; ++jj)  // wave 3's sixteenth row is its fifteenth again: the same value to the same place
+            xs[min(SF_PR * wave + jj, SF_ROWS - 1) * SF_IW + lane] = (prow[jj] >= 0 && okx) ? pp[jj] : 0.f;
+#pragma unroll
+        for (int e = 0; e < SF_XT; ++e)
+            if (tid + 256 * e < SF_EXTRA)
+                xs[xlds[e]] = (xrow[e] >= 0 && ix0 + xcol[e] >= 0 && ix0 + xcol[e] < s.W) ? pp[SF_PR + e] : 0.f;
+    };
+
+    request(0);
     for (int i = tid; i < ST_CO * ST_KP; i += 256) {
         const int co = i / ST_KP, k = i - co * ST_KP;
         wl[co * ST_WLD + k] = k < ST_KK ? wgt[co * ST_KK + k] : 0.f;
     }
-    const float* xb = x + (size_t)b * ST_CI * s.H * s.W;
-    const int iy0 = oy0 * ST_S - ST_PAD;
+    commit(0);
+    __syncthreads();
     // the two output rows of this wave, pixel li of each: patch offsets of their top-left taps
-    const int poff0 = (ST_S * (2 * wave)) * SF_IW + ST_S * li, poff1 = poff0 + ST_S * SF_IW;
+    const int poff0 = (ST_S * (2 * wave)) * SF_IW + ST_S * li;  // the second row's are ST_S * SF_IW further
+    const size_t ylane = (((size_t)b * ST_CO + 4 * h) * s.Ho + oy0 + 2 * wave) * s.Wo + li;  // channel 4 h, row 2 wave, pixel li
     for (int t = 0; t < tiles_x; ++t) {
-        const int ox0 = t * SF_TW, ix0 = ox0 * ST_S - ST_PAD;
-        __syncthreads();  // previous tile's readers are done with xs (and, first time, wl / kt are being written)
-        for (int i = tid; i < SF_PATCH; i += 256) {
-            const int ci = i / (SF_IH * SF_IW), r = i - ci * SF_IH * SF_IW, yy = r / SF_IW, xx = r - yy * SF_IW;
-            const int iy = iy0 + yy, ix = ix0 + xx;
-            xs[i] = (iy >= 0 && iy < s.H && ix >= 0 && ix < s.W) ? xb[((size_t)ci * s.H + iy) * s.W + ix] : 0.f;
-        }
-        __syncthreads();
+        const int ox0 = t * SF_TW;
+        if (t + 1 < tiles_x) request(t + 1);  // in flight underneath this tile's MFMAs
         f32x16 acc[2][2];
 #pragma unroll
         for (int i = 0; i < 2; ++i)
@@ -89,18 +147,44 @@ __global__ __launch_bounds__(256) void stem_conv_fwd_kernel(const float* __restr
                 for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
         const float* wrow = wl + li * ST_WLD + h;
         const float* xp0 = xs + poff0;
-        const float* xp1 = xs + poff1;
-#pragma unroll  // fully unrolled: the (ci,ky,kx) patch offsets of both lane halves are compile-time constants
-        for (int k0 = 0; k0 < ST_KP; k0 += 2) {
-            const int ko = h ? stem_koff(k0 + 1, SF_IH, SF_IW) : stem_koff(k0, SF_IH, SF_IW);
-            const float a0 = wrow[k0], a1 = wrow[32 * ST_WLD + k0];
-            const float b0 = xp0[ko], b1 = xp1[ko];
-            acc[0][0] = mfma32(a0, b0, acc[0][0]);
-            acc[0][1] = mfma32(a0, b1, acc[0][1]);
-            acc[1][0] = mfma32(a1, b0, acc[1][0]);
-            acc[1][1] = mfma32(a1, b1, acc[1][1]);
+        // Fully unrolled: the (ci,ky,kx) patch offsets of both lane halves are compile-time constants.  The operands of k-group
+        // g + 1 are read while group g is multiplied, and no further ahead (the scheduling barrier): with the next patch in
+        // flight the registers hold two groups' operands, not the tens the scheduler would hoist.
+        float av[2][SF_KG][2], bv[2][SF_KG][2];
+        auto read_group = [&](int g, float(*a)[2], float(*bq)[2]) {
+#pragma unroll
+            for (int i = 0; i < SF_KG; ++i) {
+                const int k0 = 2 * (SF_KG * g + i);
+                // offset of the upper lane half = that of the lower + d, and d takes four values over the 74 steps: a base per
+                // value and an immediate, not 74 per-lane offsets carried through the tile loop
+                const int kl = stem_koff(k0, SF_IH, SF_IW), d = stem_koff(k0 + 1, SF_IH, SF_IW) - kl;
+                const float* q = xp0 + (h ? d : 0);
+                a[i][0] = wrow[k0], a[i][1] = wrow[32 * ST_WLD + k0];
+                bq[i][0] = q[kl], bq[i][1] = q[kl + ST_S * SF_IW];
+            }
+        };
+        read_group(0, av[0], bv[0]);
+#pragma unroll
+        for (int g = 0; g < SF_NG; ++g) {
+            if (g + 1 < SF_NG) read_group(g + 1, av[(g + 1) & 1], bv[(g + 1) & 1]);
+#pragma unroll
+            for (int i = 0; i < SF_KG; ++i) {  // k-order 0..147
+                const float a0 = av[g & 1][i][0], a1 = av[g & 1][i][1], b0 = bv[g & 1][i][0], b1 = bv[g & 1][i][1];
+                acc[0][0] = mfma32(a0, b0, acc[0][0]);
+                acc[0][1] = mfma32(a0, b1, acc[0][1]);
+                acc[1][0] = mfma32(a1, b0, acc[1][0]);
+                acc[1][1] = mfma32(a1, b1, acc[1][1]);
+            }
+            __builtin_amdgcn_sched_barrier(0);
+        }
+        if (t + 1 < tiles_x) {
+            __syncthreads();  // this tile's readers are done with the patch
+            commit(t + 1);
         }
         const int ox = ox0 + li;
+        // the 64 store addresses are formed here from one per-lane offset, not carried (128 registers) through the tile loop
+        size_t yo = ylane + ox0;
+        asm volatile("" : "+v"(yo));
 #pragma unroll
         for (int j = 0; j < 2; ++j) {
             const int oy = oy0 + 2 * wave + j;
@@ -108,12 +192,11 @@ __global__ __launch_bounds__(256) void stem_conv_fwd_kernel(const float* __restr
 #pragma unroll
                 for (int i = 0; i < 2; ++i)
 #pragma unroll
-                    for (int r = 0; r < 16; ++r) {
-                        const int co = 32 * i + acc_row(r) + 4 * h;
-                        y[(((size_t)b * ST_CO + co) * s.Ho + oy) * s.Wo + ox] = acc[i][j][r];
-                    }
+                    for (int r = 0; r < 16; ++r)
+                        y[yo + ((size_t)(32 * i + acc_row(r)) * s.Ho + j) * s.Wo] = acc[i][j][r];
             }
         }
+        __syncthreads();  // tile t+1 is in LDS
     }
 }
 
@@ -136,12 +219,6 @@ constexpr int SW_BNP = 8;                                    // per-channel scal
 struct StemBn {
     const float *z, *mean, *invstd, *weight, *bias, *coef;
 };
-
-// load at a wave-uniform base + a 32-bit per-lane byte offset (one address register per lane, whatever the number of bases)
-template <typename T>
-__device__ __forceinline__ T sw_ld(const float* base, unsigned byte_off) {
-    return *reinterpret_cast<const T*>(reinterpret_cast<const char*>(base) + byte_off);
-}
 
 // One kernel, two operand forms: BN = false reads dy; BN = true reads (g, z) and forms dy per element on the way into LDS, so
 // the 537 MB dz of sb.conv1's BatchNorm is never written.  VEC (Wo % 4 == 0, 16-byte aligned operands): 128-bit row loads.
