@@ -186,6 +186,11 @@ hipError_t predict_argmax_run(const float* total, int N, int C, int H, int W, un
 hipError_t predict_render_run(const unsigned char* labels, const float* image, const unsigned char* palette, int n_colors,
                               const float* mean, const float* std, float alpha, int N, int H, int W, unsigned char* pred,
                               unsigned char* inp, unsigned char* ovl, hipStream_t stream);
+// augment.hip
+size_t augment_workspace(int N, int th, int tw);
+hipError_t augment_run(const void* samples, int N, int th, int tw, const float* noise, unsigned long long seed, const float* mean,
+                       const float* std, float* out_image, long long* out_label, unsigned char* out_u8, void* workspace,
+                       hipStream_t stream);
 // opt_tail.hip
 size_t sgd_tail_workspace(int n_chunks);
 size_t sgd_tail_state(int n_entries);
@@ -1479,6 +1484,40 @@ int cabinet_sgd_tail_step(const cabinet_sgd_tail_entry* entries, int n_entries, 
     return hip_status(cabinet::sgd_tail_run(entries, n_entries, chunks, n_chunks, *config, state, workspace, max_grid,
                                             static_cast<hipStream_t>(stream)),
                       "sgd_tail_step launch");
+}
+
+// ------------------------------------------------------ training augmentation (K18): the reference's Cityscapes transform
+int cabinet_augment_supported(int th, int tw, int max_taps, int max_pad_y, int max_pad_x, int min_h, int min_w) {
+    if (th < 1 || tw < 1 || th > 32768 || tw > 32768) return fail(0, "augment: crop %d x %d outside [1, 32768]", th, tw);
+    if (max_taps < 1 || max_taps > 5) return fail(0, "augment: %d taps per output pixel (1 to 5: resize ratio in/out <= 2.5)", max_taps);
+    if (min_h < 1 || min_w < 1) return fail(0, "augment: empty resized image %d x %d", min_h, min_w);
+    if (max_pad_y < 0 || max_pad_x < 0 || max_pad_y > min_h - 1 || max_pad_x > min_w - 1)
+        return fail(0, "augment: reflect padding (%d, %d) exceeds the resized size (%d, %d) - 1", max_pad_y, max_pad_x, min_h, min_w);
+    return 1;
+}
+
+size_t cabinet_augment_workspace_bytes(int N, int th, int tw) {
+    return (N > 0 && th > 0 && tw > 0) ? cabinet::augment_workspace(N, th, tw) : 0;
+}
+
+int cabinet_augment_batch(const void* samples, int N, int th, int tw, const float* noise, unsigned long long seed, const float* mean,
+                          const float* std, float* out_image, long long* out_label, unsigned char* out_u8, void* workspace,
+                          size_t workspace_bytes, cabinet_stream_t stream) {
+    if (N <= 0 || th <= 0 || tw <= 0) return fail(CABINET_ERR_INVALID_ARG, "augment_batch: non-positive dimension");
+    if (!samples || !mean || !std || !out_image || !out_label)
+        return fail(CABINET_ERR_INVALID_ARG, "augment_batch: null samples, mean, std, out_image or out_label");
+    if (!cabinet_augment_supported(th, tw, 1, 0, 0, 1, 1)) return CABINET_ERR_UNSUPPORTED;  // the message is already set
+    if (N > 65535) return fail(CABINET_ERR_UNSUPPORTED, "augment_batch: N=%d exceeds grid limits", N);
+    if ((reinterpret_cast<uintptr_t>(samples) | reinterpret_cast<uintptr_t>(out_label)) & 7)
+        return fail(CABINET_ERR_INVALID_ARG, "augment_batch: samples and out_label must be 8-byte aligned");
+    if ((reinterpret_cast<uintptr_t>(out_image) | reinterpret_cast<uintptr_t>(noise)) & 3)
+        return fail(CABINET_ERR_INVALID_ARG, "augment_batch: out_image and noise must be 4-byte aligned");
+    const size_t need = cabinet_augment_workspace_bytes(N, th, tw);
+    if (!workspace || workspace_bytes < need || (reinterpret_cast<uintptr_t>(workspace) & 15))
+        return fail(CABINET_ERR_INVALID_ARG, "augment_batch: workspace of %zu bytes (16-byte aligned) needed, got %zu", need, workspace_bytes);
+    return hip_status(cabinet::augment_run(samples, N, th, tw, noise, seed, mean, std, out_image, out_label, out_u8, workspace,
+                                           static_cast<hipStream_t>(stream)),
+                      "augment_batch launch");
 }
 
 }  // extern "C"

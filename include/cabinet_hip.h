@@ -764,6 +764,83 @@ int cabinet_sgd_tail_step(const cabinet_sgd_tail_entry* entries, int n_entries, 
                           const cabinet_sgd_tail_config* config, void* state, size_t state_bytes, int max_grid,
                           void* workspace, size_t workspace_bytes, cabinet_stream_t stream);
 
+/* ------------------------------------------------------------------------- *
+ * Training augmentation (K18; ADDITIVE to ABI version 8: no existing entry point, constant or layout changes).
+ * Replaces, for a batch, what src/datasets/cityscapes.py does to a decoded train sample: :114-136 (RandomHorizontalFlip,
+ * RandomScale, RandomCrop with reflect padding, RandomColorJitter, RandomGrayscale, RandomGamma, RandomNoise, RandomCutout of
+ * src/datasets/transform.py), :102-109 (ToTensor, Normalize) and :156-158 (convert_labels, int64) -- byte for byte, but for the
+ * VALUES of the noise when the library draws them itself.  Two launches on `stream`; nothing is allocated, nothing synchronises.
+ *
+ * samples: DEVICE memory, one block the caller builds per batch and copies once: N entries of cabinet_augment_sample, then the
+ * tables they name by BYTE OFFSET from `samples` (4-byte aligned).  Per sample:
+ *   image (H,W,3) uint8 interleaved and label (H,W) uint8, device pointers; samples of one batch may differ in H and W.
+ *   col_taps[tw], row_taps[th] of cabinet_augment_tap: output column x of the crop is, per channel,
+ *       clip8((2^21 + sum_{k<n} coef[k] * in[first + step*k]) >> 22)
+ *     (Pillow's resize(BILINEAR): horizontal pass first into a uint8 intermediate, then the vertical pass over it; coef are
+ *     Pillow's 22-bit integer coefficients).  The caller folds in the horizontal flip (step = -1 from the mirrored index), the
+ *     crop offset (only the window's entries are passed) and the reflect padding (a column past the resized width w takes the
+ *     entry of resized column 2 (w - 1) - c).  n <= 5; an unchanged axis is the single coefficient 2^22.
+ *   lab_col[tw], lab_row[th] int32: the label's source index (Pillow's resize(NEAREST), flip and crop folded in), or -1 for a
+ *     padded position, which becomes ignore_label.  Otherwise the label is label_lut[source byte] (id -> trainId).
+ *   brightness, contrast, saturation: the three ImageEnhance factors r of Image.blend(degenerate, image, r), 1 = identity.  fp32,
+ *     t = deg + r * (src - deg) with every operation rounded on its own; (uint8) t for 0 <= r <= 1, else 0 for t <= 0, 255 for
+ *     t >= 255, (uint8) t between.  Degenerates: 0; m = (int)(mean L of the brightened crop + 0.5); the pixel's own L, with
+ *     L = (19595 R + 38470 G + 7471 B + 0x8000) >> 16.
+ *   flags: CABINET_AUGMENT_GRAY (all channels = L), _GAMMA (byte -> gamma_lut[byte]; the caller builds the table with the
+ *     reference's numpy expression), _NOISE ((uint8) clip((double) byte + (double) noise, 0, 255)), _CUTOUT (zero bytes on the
+ *     square rows cut_y .. cut_y + cut_size - 1, columns cut_x .. cut_x + cut_size - 1), applied in this order after the blends.
+ * noise: NULL, or device fp32 (N,th,tw,3) of values ALREADY scaled by sigma * 255, used as given.  NULL: the library draws
+ *   standard normals -- Philox4x32-10 keyed by `seed`, counter (pixel index y tw + x, sample index), Box-Muller on the two
+ *   pairs of the block, the first three values for R, G, B -- and multiplies them by noise_scale.  Stateless, no atomics: the
+ *   same (seed, sample, pixel) gives the same bytes.
+ * mean, std: three HOST floats each, read during the call.  out_image (N,3,th,tw) fp32 = ((float) byte / 255 - mean[c]) / std[c],
+ *   two correctly rounded operations (4-byte aligned; 16-byte stores are used where an address allows them); out_label
+ *   (N,th,tw) int64; out_u8 (N,th,tw,3) uint8, the final bytes, or NULL.  No byte outside a source array is read -- every table
+ *   index is clamped into its array -- and no byte outside an output is written.
+ * workspace: cabinet_augment_workspace_bytes(N, th, tw), 16-byte aligned: the uint8 crop after the brightness blend and one
+ *   64-bit partial sum of L per workgroup tile.  Every call writes all of it before reading: the caller zeroes nothing.
+ * Coverage (cabinet_augment_supported: 1 / 0, with the reason in cabinet_last_error()): 1 <= th, tw <= 32768; max_taps <= 5;
+ *   reflect padding of an axis <= the smallest resized size - 1 (numpy's multiple reflection is out).  The limit behind the
+ *   tap count is the resize ratio in/out <= 2.5 per axis (scale >= 0.4): Pillow's tables then have at most five taps, and the
+ *   row taps of 16 consecutive output rows span fewer than 17 * 2.5 + 1 source rows, inside the 48 the geometry kernel stages
+ *   per tile.  That span (largest minus smallest source row of row_taps[16 j .. 16 j + 15], plus one, <= 48) is part of the
+ *   contract for tables built any other way: five taps alone do not imply it (a tiny output clamps its taps at the borders at
+ *   any ratio), and rows past it are read as row 47 of the tile.  The tables live in device memory, so cabinet_augment_batch
+ *   itself checks what it can see: -1 for a null pointer, a non-positive count, a misaligned pointer or a short workspace; -2
+ *   for a shape outside coverage.  The caller states the rest -- the batch's largest tap count and pads, its smallest resized
+ *   size -- to cabinet_augment_supported.
+ * ------------------------------------------------------------------------- */
+#define CABINET_AUGMENT_GRAY 1
+#define CABINET_AUGMENT_GAMMA 2
+#define CABINET_AUGMENT_NOISE 4
+#define CABINET_AUGMENT_CUTOUT 8
+
+typedef struct cabinet_augment_tap {
+    int first, step, n;
+    int coef[5];
+} cabinet_augment_tap; /* 32 bytes */
+
+typedef struct cabinet_augment_sample {
+    const unsigned char* image;
+    const unsigned char* label;
+    int H, W;
+    unsigned long long col_taps, row_taps, lab_col, lab_row; /* byte offsets from `samples` */
+    float brightness, contrast, saturation;
+    int flags;
+    float noise_scale; /* sigma * 255 */
+    int cut_y, cut_x, cut_size;
+    int ignore_label;
+    int reserved;
+    unsigned char gamma_lut[256];
+    long long label_lut[256];
+} cabinet_augment_sample; /* 2400 bytes */
+
+int cabinet_augment_supported(int th, int tw, int max_taps, int max_pad_y, int max_pad_x, int min_h, int min_w);
+size_t cabinet_augment_workspace_bytes(int N, int th, int tw);
+int cabinet_augment_batch(const void* samples, int N, int th, int tw, const float* noise, unsigned long long seed,
+                          const float* mean, const float* std, float* out_image, long long* out_label, unsigned char* out_u8,
+                          void* workspace, size_t workspace_bytes, cabinet_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
