@@ -53,6 +53,11 @@ SIGNATURES = {
     "cabinet_ohem_select": (_INT, [_PTR] * 3 + [_INT] * 5 + [_FLT] + [_INT] * 3 + [_PTR] * 3 + [_PTR, _SZ, _PTR]),
     "cabinet_ohem_up_w_bwd_sel": (_INT, [_PTR] * 3 + [_INT] * 6 + [_PTR, _INT, _FLT] + [_PTR] + [_PTR, _SZ] + [_PTR, _PTR]),
     "cabinet_ohem_up_pair_w_bwd_sel": (_INT, [_PTR] * 4 + [_INT] * 6 + [_PTR, _INT, _FLT] + [_PTR] + [_PTR, _SZ] + [_PTR, _PTR, _PTR]),
+    "cabinet_focal_up_supported": (_INT, [_INT] * 5 + [_FLT]),
+    "cabinet_focal_up_fwd": (_INT, [_PTR] * 3 + [_INT] * 6 + [_FLT, _FLT, _INT] + [_PTR] * 3 + [_PTR, _PTR, _PTR]),
+    "cabinet_focal_stats": (_INT, [_PTR, _PTR, _INT, _INT, _PTR, _PTR]),
+    "cabinet_focal_up_bwd_workspace_bytes": (_SZ, [_INT] * 7),
+    "cabinet_focal_up_bwd": (_INT, [_PTR] * 4 + [_INT] * 6 + [_FLT, _FLT, _INT, _FLT] + [_PTR] + [_PTR, _SZ] + [_PTR, _PTR, _PTR]),
     "cabinet_cab_qkv_supported": (_INT, [_INT] * 7 + [_PTR]),
     "cabinet_cab_qkv_padded_bins": (_INT, [_INT, _PTR]),
     "cabinet_cab_qkv_fwd_workspace_bytes": (_SZ, [_INT] * 7 + [_PTR]),

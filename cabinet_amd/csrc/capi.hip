@@ -147,13 +147,14 @@ hipError_t pwconv_bwd_run(const float* dy, const float* x, const float* w, int B
 int ohem_blocks(int B, int H, int W);
 hipError_t ohem_up_fwd_run(int nh, const float* const* low, const long long* labels, int B, int C, int Hl, int Wl, int H, int W,
                            float thresh, int ignore_lb, float* const* loss_px, float* const* blk_sum, int* const* blk_cnt,
-                           const float* const* class_weight, hipStream_t stream);
+                           const float* const* class_weight, hipStream_t stream, const float* focal_gamma = nullptr);
+hipError_t focal_stats_run(const float* blk_sum, const int* blk_cnt, int nheads, int nblk, double* stats, hipStream_t stream);
 hipError_t ohem_stats_run(const float* blk_sum, const int* blk_cnt, int nheads, int nblk, double* stats, hipStream_t stream);
 size_t ohem_up_bwd_workspace(int B, int C, int H, int Wl);
 bool ohem_up_supported(int C, int Wl, int W);
 hipError_t ohem_up_bwd_run(int nh, const float* const* low, const long long* labels, const float* const* loss_px, int B, int C,
                            int Hl, int Wl, int H, int W, float thresh, int ignore_lb, float coef, float* dlow, void* ws,
-                           const float* const* cw, const double* dsel, hipStream_t stream);
+                           const float* const* cw, const double* dsel, hipStream_t stream, const float* focal_gamma = nullptr);
 size_t ohem_select_workspace(int nheads);
 hipError_t ohem_select_run(int nheads, const float* const* loss_px, const long long* labels, const double* stats, long long P, int C,
                            float thresh, const int* n_min, int ignore_lb, const float* const* cw, double* sel, void* ws,
@@ -650,6 +651,77 @@ int cabinet_ohem_up_pair_w_bwd_sel(const float* logits_low_a, const float* logit
     return hip_status(cabinet::ohem_up_bwd_run(2, low, labels, lp, B, C, Hl, Wl, H, W, 0.f, ignore_lb, coef, dlogits_low,
                                                workspace, cw, sel, static_cast<hipStream_t>(stream)),
                       "ohem_up_pair_bwd_sel launch");
+}
+
+// ------------------------------------------------------ softmax focal loss + fused upsample (the OHEM kernels' focal mode)
+static bool focal_gamma_ok(float gamma) { return gamma >= 0.f && gamma <= 3.0e38f; }  // false for NaN and +inf as well
+
+int cabinet_focal_up_supported(int C, int Hl, int Wl, int H, int W, float gamma) {
+    if (!focal_gamma_ok(gamma)) {
+        fail(CABINET_ERR_UNSUPPORTED, "focal_up: gamma=%g (needs a finite gamma >= 0)", (double)gamma);
+        return 0;
+    }
+    return check_ohem(1, C, Hl, Wl, H, W) == CABINET_OK ? 1 : 0;  // check_ohem leaves its reason in cabinet_last_error()
+}
+
+int cabinet_focal_up_fwd(const float* logits_low_a, const float* logits_low_b, const long long* labels, int B, int C, int Hl,
+                         int Wl, int H, int W, float gamma_a, float gamma_b, int ignore_lb, float* loss_px, float* blk_sum,
+                         int* blk_cnt, const float* class_weight_a, const float* class_weight_b, cabinet_stream_t stream) {
+    if (int rc = check_ohem(B, C, Hl, Wl, H, W)) return rc;
+    const int nh = logits_low_b ? 2 : 1;
+    if (!focal_gamma_ok(gamma_a) || (nh == 2 && !focal_gamma_ok(gamma_b)))
+        return fail(CABINET_ERR_UNSUPPORTED, "focal_up_fwd: gamma=%g / %g (needs a finite gamma >= 0)", (double)gamma_a,
+                    (double)gamma_b);
+    if (!logits_low_a || !labels || !loss_px || !blk_sum || !blk_cnt)
+        return fail(CABINET_ERR_INVALID_ARG, "focal_up_fwd: null tensor pointer");
+    CABINET_REQUIRE_ALIGNED("focal_up_fwd", logits_low_a, logits_low_b, labels, loss_px, blk_sum);
+    const int nblk = cabinet::ohem_blocks(B, H, W);
+    const float* low[2] = {logits_low_a, logits_low_b};
+    float* lp[2] = {loss_px, loss_px + (size_t)B * H * W};
+    float* bs[2] = {blk_sum, blk_sum + 2 * (size_t)nblk};
+    int* bc[2] = {blk_cnt, blk_cnt + nblk};
+    const float* cw[2] = {class_weight_a, class_weight_b};
+    const float gm[2] = {gamma_a, gamma_b};
+    return hip_status(cabinet::ohem_up_fwd_run(nh, low, labels, B, C, Hl, Wl, H, W, 0.f, ignore_lb, lp, bs, bc, cw,
+                                               static_cast<hipStream_t>(stream), gm),
+                      "focal_up_fwd launch");
+}
+
+int cabinet_focal_stats(const float* blk_sum, const int* blk_cnt, int nheads, int nblk, double* stats, cabinet_stream_t stream) {
+    if (nheads <= 0 || nheads > 65535 || nblk <= 0) return fail(CABINET_ERR_INVALID_ARG, "focal_stats: nheads=%d nblk=%d", nheads, nblk);
+    if (!blk_sum || !blk_cnt || !stats) return fail(CABINET_ERR_INVALID_ARG, "focal_stats: null tensor pointer");
+    if ((reinterpret_cast<uintptr_t>(blk_sum) & 7) != 0) return fail(CABINET_ERR_INVALID_ARG, "focal_stats: blk_sum is not 8-byte aligned");
+    return hip_status(cabinet::focal_stats_run(blk_sum, blk_cnt, nheads, nblk, stats, static_cast<hipStream_t>(stream)),
+                      "focal_stats launch");
+}
+
+size_t cabinet_focal_up_bwd_workspace_bytes(int nheads, int B, int C, int Hl, int Wl, int H, int W) {
+    if (nheads < 1 || nheads > 2) return 0;
+    return (size_t)nheads * cabinet_ohem_up_bwd_workspace_bytes(B, C, Hl, Wl, H, W);
+}
+
+int cabinet_focal_up_bwd(const float* logits_low_a, const float* logits_low_b, const long long* labels, const float* loss_px,
+                         int B, int C, int Hl, int Wl, int H, int W, float gamma_a, float gamma_b, int ignore_lb, float coef,
+                         float* dlogits_low, void* workspace, size_t workspace_bytes, const float* class_weight_a,
+                         const float* class_weight_b, cabinet_stream_t stream) {
+    if (int rc = check_ohem(B, C, Hl, Wl, H, W)) return rc;
+    const int nh = logits_low_b ? 2 : 1;
+    if (!focal_gamma_ok(gamma_a) || (nh == 2 && !focal_gamma_ok(gamma_b)))
+        return fail(CABINET_ERR_UNSUPPORTED, "focal_up_bwd: gamma=%g / %g (needs a finite gamma >= 0)", (double)gamma_a,
+                    (double)gamma_b);
+    if (!logits_low_a || !labels || !loss_px || !dlogits_low)
+        return fail(CABINET_ERR_INVALID_ARG, "focal_up_bwd: null tensor pointer");
+    CABINET_REQUIRE_ALIGNED("focal_up_bwd", logits_low_a, logits_low_b, labels, loss_px, dlogits_low);
+    const size_t need = cabinet_focal_up_bwd_workspace_bytes(nh, B, C, Hl, Wl, H, W);
+    if (!workspace || workspace_bytes < need)
+        return fail(CABINET_ERR_WORKSPACE, "focal_up_bwd: workspace %zu < %zu bytes", workspace_bytes, need);
+    const float* low[2] = {logits_low_a, logits_low_b};
+    const float* lp[2] = {loss_px, loss_px + (size_t)B * H * W};
+    const float* cw[2] = {class_weight_a, class_weight_b};
+    const float gm[2] = {gamma_a, gamma_b};
+    return hip_status(cabinet::ohem_up_bwd_run(nh, low, labels, lp, B, C, Hl, Wl, H, W, 0.f, ignore_lb, coef, dlogits_low,
+                                               workspace, cw, nullptr, static_cast<hipStream_t>(stream), gm),
+                      "focal_up_bwd launch");
 }
 
 // ------------------------------------------------------ CAB local branch + block output

@@ -28,17 +28,71 @@
 #include <stdint.h>
 #include <stdlib.h>
 
+#include <type_traits>
+
 #include "common.hpp"
 
 namespace cabinet {
 
-// per-head class-weight tables ((C,) fp32 device pointers; null = that head is unweighted)
-struct OhemWeights {
+// per-head class-weight tables ((C,) fp32 device pointers; null = that head is unweighted).  The focal instantiations
+// (FL = true, below) carry each head's exponent behind the tables; the kernel arguments of every other instantiation are
+// the two pointers they always were.
+template <bool FL>
+struct OhemFactorT {
     const float* w[2];
 };
+template <>
+struct OhemFactorT<true> {
+    const float* w[2];
+    float gamma[2];
+};
+using OhemWeights = OhemFactorT<false>;
+using FocalHeads = OhemFactorT<true>;
+
+template <bool FL>
+__host__ __device__ __forceinline__ OhemFactorT<FL> ohem_one_head(const OhemFactorT<FL>& f, int i) {
+    OhemFactorT<FL> r = f;
+    r.w[0] = f.w[i], r.w[1] = nullptr;
+    if constexpr (FL) r.gamma[0] = f.gamma[i];
+    return r;
+}
+
+// last argument of the general forward kernel for head i: the bare table, or the focal head
+__host__ __forceinline__ const float* ohem_fwd_table(const OhemWeights& f, int i) { return f.w[i]; }
+__host__ __forceinline__ FocalHeads ohem_fwd_table(const FocalHeads& f, int i) { return ohem_one_head(f, i); }
 
 // the weighted per-pixel loss: ONE expression for the forward's statistics and for every backward kernel's selection
 __device__ __forceinline__ float ohem_weighted(float w, float loss) { return w * loss; }
+
+// ---- focal mode (FL = true): SoftmaxFocalLoss of reference loss.py:86-127 on the same fused operator.
+// Per valid pixel l = lse - x_t (what loss_px holds), p = exp(-l), q = 1 - p; per head D = sum w_t, S = sum w_t q^gamma l,
+// loss = S / D, and dloss/dz = (g / D) U^T[w_t a (softmax - onehot)] with a = q^gamma + gamma p q^(gamma-1) l >= 0: the OHEM
+// backward with the per-pixel factor cf = w_t a(l) (0 switches the pixel off).  The forward and every backward kernel form q
+// and a with the functions below.
+//   q = -expm1(-l); 1 - exp(-l) is used only where it cancels nothing: a confident pixel (l ~ 1e-6) would lose every digit
+//       of q.  From l = 1/8 on the difference 1 - exp(-l) >= 0.117 keeps all but three bits (v_exp_f32, 1 ulp of p: <= 5e-7 of
+//       q); below, the alternating series in nested form, l (1 - l/2 (1 - l/3 (... (1 - l/6)))), whose first dropped term is
+//       below l^6 / 7! < 8e-10 of q.  A few registers and no call (the library's expm1f is a longer sequence with more scalar
+//       constants).  l can round to a few ulp below 0; q is clamped at 0.
+//   q^gamma = exp2(gamma log2 q): two transcendentals per pixel and head (beside C exps).  q^0 = 1 also at q = 0 (torch's
+//       0 ** 0); gamma > 0 and q = 0 give 0.
+//   a = q^gamma (1 + gamma p l / q): q^(gamma-1) is never formed on its own (l / q -> 1 as q -> 0).  At q = 0: a = 1 for
+//       gamma = 0 and a = 0 for gamma > 0, also for 0 < gamma < 1 where the reference's fp32 autograd returns NaN (0^(gamma-1) 0).
+__device__ __forceinline__ float focal_q(float l) {
+    float s = 1.f - l * (1.f / 6.f);
+#pragma unroll
+    for (int k = 5; k >= 2; --k) s = 1.f - (l * (1.f / (float)k)) * s;
+    const float q = l >= 0.125f ? 1.f - fast_exp2(-l * LOG2E_F) : l * s;
+    return fmaxf(q, 0.f);
+}
+__device__ __forceinline__ float focal_pow(float q, float gamma) {
+    // q >= 0 (focal_q): v_log_f32(0) = -inf, gamma > 0 times it stays -inf and v_exp_f32(-inf) = 0; only gamma = 0 needs a guard
+    return gamma == 0.f ? 1.f : fast_exp2(gamma * fast_log2(q));
+}
+__device__ __forceinline__ float focal_factor(float l, float gamma) {
+    const float q = focal_q(l), qg = focal_pow(q, gamma);
+    return q > 0.f ? qg * (1.f + gamma * ((1.f - q) * l / q)) : qg;
+}
 
 
 // One workgroup per output row (b, oy).  The two source rows are lerped vertically into LDS once (coalesced
@@ -46,14 +100,27 @@ __device__ __forceinline__ float ohem_weighted(float w, float loss) { return w *
 // CMAX: classes rounded up, the per-class loops are fully unrolled.  EXACT (C == CMAX: 8 and 19 classes have their own
 // instances) drops the `c < C` predicates: with a run-time C the compiler turns every class into its own uniform branch
 // (LDS read -> wait -> arithmetic, one class at a time); without them the 2 C LDS reads of a pixel are in flight together.
-template <int CMAX, bool EXACT, bool WT>
-__global__ __launch_bounds__(256) void ohem_up_fwd_kernel(const float* __restrict__ low, const long long* __restrict__ labels,
+// FL (focal mode, always with WT): the last argument is the head's (table, gamma) as in every other focal kernel instead of the
+// bare table, `thresh` is not read; partials are blk_sum[blk] = {sum w_t, sum w_t q^gamma l} and ONE count per block,
+// blk_cnt[blk] = #valid (poisoned as below).
+template <bool FL>
+using OhemFwdTable = std::conditional_t<FL, FocalHeads, const float* __restrict__>;
+template <int CMAX, bool EXACT, bool WT, bool FL = false>
+// (waves_per_eu: the focal instance with 20 class slots needs 102 scalar registers, its sibling 98, and 100 is where the eighth
+// wave per SIMD goes; asked for 8, the compiler keeps 17 scalars in lanes of a vector register -- no scratch -- and fits.  0 = no
+// request: every other instantiation is compiled as it was.)
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((FL && CMAX == 20) ? 8 : 0)))
+void ohem_up_fwd_kernel(const float* __restrict__ low, const long long* __restrict__ labels,
                                                            int C, int Hl, int Wl, int H, int W, float rh, float rw,
                                                            float thresh, int ignore_lb, float* __restrict__ loss_px,
                                                            float* __restrict__ blk_sum, int* __restrict__ blk_cnt,
-                                                           const float* __restrict__ cw) {
+                                                           OhemFwdTable<FL> cwp) {
     extern __shared__ __attribute__((aligned(16))) float v[];  // [C][Wl] (+ [32] class weights when WT)
-    __shared__ float s_f[4];
+    __shared__ float s_f[FL ? 8 : 4];
+    const float* __restrict__ cw;
+    float gamma = 0.f;
+    if constexpr (FL) cw = cwp.w[0], gamma = cwp.gamma[0];
+    else cw = cwp;
     __shared__ int s_i[3][4];
     const int b = blockIdx.y, oy = blockIdx.x, P = H * W;
     const size_t plane = (size_t)Hl * Wl;
@@ -71,12 +138,12 @@ __global__ __launch_bounds__(256) void ohem_up_fwd_kernel(const float* __restric
         if (threadIdx.x < 32) sw[threadIdx.x] = (cw && (int)threadIdx.x < C) ? cw[threadIdx.x] : 1.f;
     }
     __syncthreads();
-    float my_sum = 0.f;
+    float my_sum = 0.f, my_den = 0.f;
     int my_valid = 0, my_above = 0, my_bad = 0;
     for (int ox = threadIdx.x; ox < W; ox += 256) {
         const size_t pix = (size_t)b * P + (size_t)oy * W + ox;
         const long long lb = labels[pix];
-        float loss = 0.f;
+        float loss = 0.f, fw = 0.f;  // fw (FL): the pixel's class weight, 0 for an ignored pixel
         if (lb != (long long)ignore_lb) {
             int x0, x1;
             float lx;
@@ -99,17 +166,26 @@ __global__ __launch_bounds__(256) void ohem_up_fwd_kernel(const float* __restric
             // arithmetic sentinel summed over a wide row could wrap)
             my_valid += 1;
             my_bad |= (lb < 0 || lb >= (long long)C) ? 1 : 0;
-            float wloss = loss;
-            if constexpr (WT) wloss = ohem_weighted((lb >= 0 && lb < (long long)C) ? sw[(int)lb] : 1.f, loss);
-            if (wloss > thresh) {
-                my_above += 1;
-                my_sum += wloss;
+            if constexpr (FL) {
+                fw = (lb >= 0 && lb < (long long)C) ? sw[(int)lb] : 1.f;  // the label is clamped before it indexes
+            } else {
+                float wloss = loss;
+                if constexpr (WT) wloss = ohem_weighted((lb >= 0 && lb < (long long)C) ? sw[(int)lb] : 1.f, loss);
+                if (wloss > thresh) {
+                    my_above += 1;
+                    my_sum += wloss;
+                }
             }
+        }
+        if constexpr (FL) {  // outside the divergent part (an ignored pixel adds 0 * 0): fewer live registers inside it
+            my_den += fw;
+            my_sum += fw * (focal_pow(focal_q(loss), gamma) * loss);
         }
         loss_px[pix] = loss;  // unweighted, also when WT
     }
     // ordered block reduction
     my_sum = wave_sum(my_sum);
+    if constexpr (FL) my_den = wave_sum(my_den);
 #pragma unroll
     for (int o = 32; o >= 1; o >>= 1) {
         my_valid += __shfl_xor(my_valid, o, 64);
@@ -118,6 +194,7 @@ __global__ __launch_bounds__(256) void ohem_up_fwd_kernel(const float* __restric
     }
     if ((threadIdx.x & 63) == 0) {
         s_f[threadIdx.x >> 6] = my_sum;
+        if constexpr (FL) s_f[4 + (threadIdx.x >> 6)] = my_den;
         s_i[0][threadIdx.x >> 6] = my_valid;
         s_i[1][threadIdx.x >> 6] = my_above;
         s_i[2][threadIdx.x >> 6] = my_bad;
@@ -125,11 +202,17 @@ __global__ __launch_bounds__(256) void ohem_up_fwd_kernel(const float* __restric
     __syncthreads();
     if (threadIdx.x == 0) {
         const int blk = blockIdx.y * gridDim.x + blockIdx.x;
-        blk_sum[blk] = (s_f[0] + s_f[1]) + (s_f[2] + s_f[3]);
         const int nv = s_i[0][0] + s_i[0][1] + s_i[0][2] + s_i[0][3];
         const int bad = s_i[2][0] | s_i[2][1] | s_i[2][2] | s_i[2][3];
-        blk_cnt[2 * blk] = bad ? -(1 << 30) : nv;  // < 0: the block saw an out-of-range label
-        blk_cnt[2 * blk + 1] = s_i[1][0] + s_i[1][1] + s_i[1][2] + s_i[1][3];
+        if constexpr (FL) {
+            blk_sum[2 * blk] = (s_f[4] + s_f[5]) + (s_f[6] + s_f[7]);
+            blk_sum[2 * blk + 1] = (s_f[0] + s_f[1]) + (s_f[2] + s_f[3]);
+            blk_cnt[blk] = bad ? -(1 << 30) : nv;
+        } else {
+            blk_sum[blk] = (s_f[0] + s_f[1]) + (s_f[2] + s_f[3]);
+            blk_cnt[2 * blk] = bad ? -(1 << 30) : nv;  // < 0: the block saw an out-of-range label
+            blk_cnt[2 * blk + 1] = s_i[1][0] + s_i[1][1] + s_i[1][2] + s_i[1][3];
+        }
     }
 }
 
@@ -148,12 +231,14 @@ struct OhemFwdHeads {
     int* blk_cnt[NH];       // (nblk,2)
 };
 
-template <int CMAX, bool EXACT, int NH, bool WT>
+// FL (focal mode, always with WT): gamma per head in cw; blk_sum[hh] is (nblk,2) = {sum w_t, sum w_t q^gamma l}, blk_cnt[hh] is
+// (nblk) = #valid (poisoned as below); `thresh` is not read.
+template <int CMAX, bool EXACT, int NH, bool WT, bool FL = false>
 __global__ __launch_bounds__(256) void ohem_up_fwd_x8_kernel(OhemFwdHeads<NH> hd, const long long* __restrict__ labels, int C,
                                                               int Hl, int Wl, int H, int W, float rh, float thresh,
-                                                              int ignore_lb, OhemWeights cw) {
+                                                              int ignore_lb, OhemFactorT<FL> cw) {
     extern __shared__ __attribute__((aligned(16))) float v[];  // [NH][C][Wl] (+ [NH][32] class weights when WT)
-    __shared__ float s_f[NH][4];
+    __shared__ float s_f[NH][FL ? 8 : 4];
     __shared__ int s_i[NH][3][4];
     // Grid (H, B) decoded XCD-aware (round 5): the dispatcher deals blocks round-robin over the 8 XCDs, so with
     // oy = blockIdx.x the eight output rows that lerp the SAME two source rows ran on eight different XCDs and every private L2
@@ -212,10 +297,10 @@ __global__ __launch_bounds__(256) void ohem_up_fwd_x8_kernel(OhemFwdHeads<NH> hd
         }
     }
     __syncthreads();
-    float my_sum[NH];
+    float my_sum[NH], my_den[NH];
     int my_valid = 0, my_bad = 0, my_above[NH];
 #pragma unroll
-    for (int hh = 0; hh < NH; ++hh) my_sum[hh] = 0.f, my_above[hh] = 0;
+    for (int hh = 0; hh < NH; ++hh) my_sum[hh] = 0.f, my_den[hh] = 0.f, my_above[hh] = 0;
     for (int g = threadIdx.x; g < Wl; g += nt) {
         const size_t pix = (size_t)b * P + (size_t)oy * W + 8 * g;  // 64-byte aligned labels, 32-byte aligned losses
         long long lb[8];
@@ -300,11 +385,17 @@ __global__ __launch_bounds__(256) void ohem_up_fwd_x8_kernel(OhemFwdHeads<NH> hd
                         lse = pm + fast_log2(s2);
                     }
                     loss = ((big[hh] - xl) + lse) * LN2_F;
-                    float wloss = loss;
-                    if constexpr (WT) wloss = ohem_weighted(sw[hh * 32 + lcls], loss);
-                    if (wloss > thresh) {
-                        my_above[hh] += 1;
-                        my_sum[hh] += wloss;
+                    if constexpr (FL) {
+                        const float w = inrange ? sw[hh * 32 + lcls] : 1.f;  // as the general forward and the backward kernels
+                        my_den[hh] += w;
+                        my_sum[hh] += w * (focal_pow(focal_q(loss), cw.gamma[hh]) * loss);
+                    } else {
+                        float wloss = loss;
+                        if constexpr (WT) wloss = ohem_weighted(sw[hh * 32 + lcls], loss);
+                        if (wloss > thresh) {
+                            my_above[hh] += 1;
+                            my_sum[hh] += wloss;
+                        }
                     }
                 }
                 out[hh][j] = loss;  // unweighted, also when WT
@@ -320,6 +411,10 @@ __global__ __launch_bounds__(256) void ohem_up_fwd_x8_kernel(OhemFwdHeads<NH> hd
     // ordered block reduction
 #pragma unroll
     for (int hh = 0; hh < NH; ++hh) my_sum[hh] = wave_sum(my_sum[hh]);
+    if constexpr (FL) {
+#pragma unroll
+        for (int hh = 0; hh < NH; ++hh) my_den[hh] = wave_sum(my_den[hh]);
+    }
 #pragma unroll
     for (int o = 32; o >= 1; o >>= 1) {
         my_valid += __shfl_xor(my_valid, o, 64);
@@ -332,6 +427,7 @@ __global__ __launch_bounds__(256) void ohem_up_fwd_x8_kernel(OhemFwdHeads<NH> hd
 #pragma unroll
         for (int hh = 0; hh < NH; ++hh) {
             s_f[hh][threadIdx.x >> 6] = my_sum[hh];
+            if constexpr (FL) s_f[hh][4 + (threadIdx.x >> 6)] = my_den[hh];
             s_i[hh][0][threadIdx.x >> 6] = my_valid;
             s_i[hh][1][threadIdx.x >> 6] = my_above[hh];
             s_i[hh][2][threadIdx.x >> 6] = my_bad;
@@ -343,9 +439,17 @@ __global__ __launch_bounds__(256) void ohem_up_fwd_x8_kernel(OhemFwdHeads<NH> hd
         float fs = 0.f;
         int nv = 0, na = 0, bad = 0;
         for (int w = 0; w < nw; ++w) fs += s_f[hh][w], nv += s_i[hh][0][w], na += s_i[hh][1][w], bad |= s_i[hh][2][w];
-        hd.blk_sum[hh][blk] = fs;
-        hd.blk_cnt[hh][2 * blk] = bad ? -(1 << 30) : nv;  // < 0: the block saw an out-of-range label
-        hd.blk_cnt[hh][2 * blk + 1] = na;
+        if constexpr (FL) {
+            float fd = 0.f;
+            for (int w = 0; w < nw; ++w) fd += s_f[hh][4 + w];
+            hd.blk_sum[hh][2 * blk] = fd;
+            hd.blk_sum[hh][2 * blk + 1] = fs;
+            hd.blk_cnt[hh][blk] = bad ? -(1 << 30) : nv;
+        } else {
+            hd.blk_sum[hh][blk] = fs;
+            hd.blk_cnt[hh][2 * blk] = bad ? -(1 << 30) : nv;  // < 0: the block saw an out-of-range label
+            hd.blk_cnt[hh][2 * blk + 1] = na;
+        }
     }
 }
 
@@ -379,11 +483,13 @@ struct OhemBwdHeads {
 // DS (device selection): the threshold is not a host scalar but row `head` of sel (nheads,4) double = [t, tie, denom, value]
 // written by the selection kernels below (ohem_select_run): a pixel counts with factor 1 when l > t, `tie` when l == t, else 0,
 // and that factor rides on the per-pixel class-weight factor cf.  DS = false is the code as it was (`thresh` by value).
-template <int CMAX, bool EXACT, int FR, bool WT, bool DS>
+// FL (focal mode, always with WT and without DS): the per-pixel factor is cf = coef w[label] a(loss_px) with the head's gamma
+// from cw; a pixel with cf = 0 is switched off like an unselected one.  `thresh` and `dsel` are not read.
+template <int CMAX, bool EXACT, int FR, bool WT, bool DS, bool FL = false>
 __global__ __launch_bounds__(OBX_T) void ohem_up_bwd_x_kernel(OhemBwdHeads hd, const long long* __restrict__ labels, int NH, int B,
                                                              int C, int Hl, int Wl, int H, int W, float rh, float rw, float thresh,
                                                              int ignore_lb, float coef, int SX, int nox_max, int R_,
-                                                             int gplane, OhemWeights cw, const double* __restrict__ dsel) {
+                                                             int gplane, OhemFactorT<FL> cw, const double* __restrict__ dsel) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int R = FR ? FR : R_;
     const int nseg = (Wl + SX - 1) / SX, items = nseg * H * B, per_xcd = (items + 7) >> 3;
@@ -440,7 +546,12 @@ __global__ __launch_bounds__(OBX_T) void ohem_up_bwd_x_kernel(OhemBwdHeads hd, c
             const size_t pix = (size_t)b * P + (size_t)oy * W + ox;
             lb = labels[pix];
             loss = loss_px[pix];
-            if constexpr (DS) {
+            if constexpr (FL) {
+                const float wl = (lb >= 0 && lb < (long long)C) ? sw[(int)lb] : 1.f;
+                const float wa = wl * focal_factor(loss, cw.gamma[head]);  // the on / off test does not see the caller's coef
+                sel = lb != (long long)ignore_lb && wa > 0.f;
+                cf = coef * wa;
+            } else if constexpr (DS) {
                 float wl = 1.f;
                 if constexpr (WT) wl = (lb >= 0 && lb < (long long)C) ? sw[(int)lb] : 1.f;
                 const float l = WT ? ohem_weighted(wl, loss) : loss;
@@ -535,10 +646,12 @@ __global__ __launch_bounds__(OBX_T) void ohem_up_bwd_x_kernel(OhemBwdHeads hd, c
 // it with all 64 lanes (Wl is a multiple of 64), so the lanes the shuffle reads from are active.
 // DS: as in the segment kernel -- [t, tie] of the head come from sel on the device; the factor f in {1, tie} multiplies the
 // class weight (lse - log2(w f) in the shift, w f (1 - lam) in the one-hot sums; f = 1 leaves both products as they were).
-template <int IPL, bool WT, bool DS>
+// FL (focal mode, always with WT and without DS): the pixel's factor is w[label] a(loss_px) with the head's gamma from cw,
+// carried exactly as w f is carried for DS (0 -> +inf in the shift: the pixel is off).
+template <int IPL, bool WT, bool DS, bool FL = false>
 __global__ __launch_bounds__(256) void ohem_up_bwd_x8row_kernel(OhemBwdHeads hd, const long long* __restrict__ labels, int NH,
                                                                 int B, int C, int Hl, int H, float rh, float thresh,
-                                                                int ignore_lb, float coef, OhemWeights cw,
+                                                                int ignore_lb, float coef, OhemFactorT<FL> cw,
                                                                 const double* __restrict__ dsel) {
     constexpr int Wl = 64 * IPL, W = 8 * Wl;
     extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -616,7 +729,10 @@ __global__ __launch_bounds__(256) void ohem_up_bwd_x8row_kernel(OhemBwdHeads hd,
             float wl = 1.f;
             if constexpr (WT) wl = __shfl(wreg, inrange ? (int)lb[j] : 0, 64);
             bool sel;
-            if constexpr (DS) {
+            if constexpr (FL) {
+                wl = wl * focal_factor(ls[j], cw.gamma[head]);  // from here on the pixel's factor is w a
+                sel = lb[j] != (long long)ignore_lb && wl > 0.f;
+            } else if constexpr (DS) {
                 const float l = WT ? ohem_weighted(wl, ls[j]) : ls[j];
                 const float f = l > thresh ? 1.f : (l == thresh ? tie : 0.f);
                 sel = lb[j] != (long long)ignore_lb && f > 0.f;
@@ -765,11 +881,14 @@ constexpr size_t OHEM_WT_LDS = 32 * sizeof(float);
 
 // nh = 1 | 2 heads over the same labels; head i: low[i] -> loss_px[i], blk_sum[i], blk_cnt[i]; cw: null, or nh class-weight tables
 // (each (C,) or null).  All null = the unweighted instantiations, untouched by the weighted ones.
+// gamma: null, or nh focal exponents -> the focal instantiations (always weighted: a null table reads as ones); blk_sum[i] is
+// then (nblk,2), blk_cnt[i] (nblk), and `thresh` is not used.
 hipError_t ohem_up_fwd_run(int nh, const float* const* low, const long long* labels, int B, int C, int Hl, int Wl, int H, int W,
                            float thresh, int ignore_lb, float* const* loss_px, float* const* blk_sum, int* const* blk_cnt,
-                           const float* const* cw, hipStream_t stream) {
+                           const float* const* cw, hipStream_t stream, const float* gamma) {
     const OhemWeights wts{{cw ? cw[0] : nullptr, (cw && nh == 2) ? cw[1] : nullptr}};
-    const bool wt = wts.w[0] || wts.w[1];
+    const FocalHeads fws{{wts.w[0], wts.w[1]}, {gamma ? gamma[0] : 0.f, (gamma && nh == 2) ? gamma[1] : 0.f}};
+    const bool wt = wts.w[0] || wts.w[1] || gamma;
     const size_t wlds = wt ? OHEM_WT_LDS : 0;
     // the x8 form needs 16-byte aligned label / loss rows (W % 8 == 0 holds) and one thread per source column
     bool x8 = Wl > 0 && W == 8 * Wl && (reinterpret_cast<uintptr_t>(labels) & 15) == 0;
@@ -777,33 +896,35 @@ hipError_t ohem_up_fwd_run(int nh, const float* const* low, const long long* lab
     const int nt8 = Wl >= 256 ? 256 : ((Wl + 63) / 64) * 64;
     // both heads in one workgroup (shared label tile, two independent exp / log chains per thread) when their row buffers fit
     const bool pair = nh == 2 && x8 && (size_t)2 * C * Wl * sizeof(float) + 2 * wlds <= 60 * 1024;
-#define OHEM_FWD_(CM, EX, WTV)                                                                                          \
+    // FLV: the focal instantiations take their heads' (table, gamma) in FS
+#define OHEM_FWD_(CM, EX, WTV, FLV, FS)                                                                                 \
     do {                                                                                                                \
         if (pair) {                                                                                                     \
             OhemFwdHeads<2> hd{{low[0], low[1]}, {loss_px[0], loss_px[1]}, {blk_sum[0], blk_sum[1]}, {blk_cnt[0], blk_cnt[1]}}; \
-            hipLaunchKernelGGL((ohem_up_fwd_x8_kernel<CM, EX, 2, WTV>), dim3(H, B), dim3(nt8),                          \
+            hipLaunchKernelGGL((ohem_up_fwd_x8_kernel<CM, EX, 2, WTV, FLV>), dim3(H, B), dim3(nt8),                     \
                                (size_t)2 * C * Wl * sizeof(float) + 2 * wlds, stream, hd, labels, C, Hl, Wl, H, W,       \
-                               (float)Hl / (float)H, thresh, ignore_lb, wts);                                            \
+                               (float)Hl / (float)H, thresh, ignore_lb, FS);                                             \
         } else {                                                                                                        \
             for (int i = 0; i < nh; ++i) {                                                                              \
                 if (x8) {                                                                                               \
                     OhemFwdHeads<1> hd{{low[i]}, {loss_px[i]}, {blk_sum[i]}, {blk_cnt[i]}};                             \
-                    hipLaunchKernelGGL((ohem_up_fwd_x8_kernel<CM, EX, 1, WTV>), dim3(H, B), dim3(nt8),                  \
+                    hipLaunchKernelGGL((ohem_up_fwd_x8_kernel<CM, EX, 1, WTV, FLV>), dim3(H, B), dim3(nt8),             \
                                        (size_t)C * Wl * sizeof(float) + wlds, stream, hd, labels, C, Hl, Wl, H, W,       \
-                                       (float)Hl / (float)H, thresh, ignore_lb, OhemWeights{{wts.w[i], nullptr}});       \
+                                       (float)Hl / (float)H, thresh, ignore_lb, ohem_one_head(FS, i));                   \
                 } else {                                                                                                \
-                    hipLaunchKernelGGL((ohem_up_fwd_kernel<CM, EX, WTV>), dim3(H, B), dim3(256),                        \
+                    hipLaunchKernelGGL((ohem_up_fwd_kernel<CM, EX, WTV, FLV>), dim3(H, B), dim3(256),                   \
                                        (size_t)C * Wl * sizeof(float) + wlds, stream, low[i], labels, C, Hl, Wl, H, W,   \
                                        (float)Hl / (float)H, (float)Wl / (float)W, thresh, ignore_lb, loss_px[i],        \
-                                       blk_sum[i], blk_cnt[i], wts.w[i]);                                                \
+                                       blk_sum[i], blk_cnt[i], ohem_fwd_table(FS, i));                                   \
                 }                                                                                                       \
             }                                                                                                           \
         }                                                                                                               \
     } while (0)
 #define OHEM_FWD(CM, EX)                                                                                                \
     do {                                                                                                                \
-        if (wt) OHEM_FWD_(CM, EX, true);                                                                                \
-        else OHEM_FWD_(CM, EX, false);                                                                                  \
+        if (gamma) OHEM_FWD_(CM, EX, true, true, fws);                                                                  \
+        else if (wt) OHEM_FWD_(CM, EX, true, false, wts);                                                               \
+        else OHEM_FWD_(CM, EX, false, false, wts);                                                                      \
     } while (0)
     if (C == 8) OHEM_FWD(8, true);
     else if (C == 19) OHEM_FWD(19, true);
@@ -857,9 +978,11 @@ static bool os_row_kernel_enabled() {
 // the forward that wrote loss_px was given: the selection is re-evaluated from them)
 hipError_t ohem_up_bwd_run(int nh, const float* const* low, const long long* labels, const float* const* loss_px, int B, int C,
                            int Hl, int Wl, int H, int W, float thresh, int ignore_lb, float coef, float* dlow, void* ws,
-                           const float* const* cw, const double* dsel, hipStream_t stream) {
+                           const float* const* cw, const double* dsel, hipStream_t stream, const float* gamma) {
+    // gamma: null, or nh focal exponents -> the focal instantiations (always weighted, never with dsel; `thresh` is not used)
     const OhemWeights wts{{cw ? cw[0] : nullptr, (cw && nh == 2) ? cw[1] : nullptr}};
-    const bool wt = wts.w[0] || wts.w[1];
+    const FocalHeads fws{{wts.w[0], wts.w[1]}, {gamma ? gamma[0] : 0.f, (gamma && nh == 2) ? gamma[1] : 0.f}};
+    const bool wt = wts.w[0] || wts.w[1] || gamma;
     float* T = static_cast<float*>(ws);
     const size_t slab = ohem_up_bwd_workspace(B, C, H, Wl) / sizeof(float);
     OhemBwdHeads hd{};
@@ -881,45 +1004,48 @@ hipError_t ohem_up_bwd_run(int nh, const float* const* low, const long long* lab
         const int rgrid = 8 * nh * ceil_div(H * B, 8);
         static lds_attr_mask m1{0}, m2{0}, m4{0}, mw1{0}, mw2{0}, mw4{0};
         static lds_attr_mask d1{0}, d2{0}, d4{0}, dw1{0}, dw2{0}, dw4{0};  // the device-selection instantiations
-#define OHEM_ROW_(I, WTV, DSV, M)                                                                                        \
+        static lds_attr_mask f1{0}, f2{0}, f4{0};                          // the focal instantiations
+#define OHEM_ROW_(I, WTV, DSV, FLV, FS, M)                                                                               \
         do {                                                                                                             \
-            if (hipError_t e = ensure_dynamic_lds(reinterpret_cast<const void*>(ohem_up_bwd_x8row_kernel<I, WTV, DSV>), 64 * 1024, M); \
+            if (hipError_t e = ensure_dynamic_lds(reinterpret_cast<const void*>(ohem_up_bwd_x8row_kernel<I, WTV, DSV, FLV>), 64 * 1024, M); \
                 e != hipSuccess)                                                                                         \
                 return e;                                                                                                \
-            hipLaunchKernelGGL((ohem_up_bwd_x8row_kernel<I, WTV, DSV>), dim3(rgrid), dim3(256), lds_row, stream, hd, labels, nh, B, \
-                               C, Hl, H, (float)Hl / (float)H, thresh, ignore_lb, coef, wts, dsel);                      \
+            hipLaunchKernelGGL((ohem_up_bwd_x8row_kernel<I, WTV, DSV, FLV>), dim3(rgrid), dim3(256), lds_row, stream, hd, labels, nh, B, \
+                               C, Hl, H, (float)Hl / (float)H, thresh, ignore_lb, coef, FS, dsel);                       \
         } while (0)
-#define OHEM_ROW(I, M, MW, D, DW)                                                                                        \
+#define OHEM_ROW(I, M, MW, D, DW, F)                                                                                     \
         do {                                                                                                             \
-            if (dsel && wt) OHEM_ROW_(I, true, true, DW);                                                                \
-            else if (dsel) OHEM_ROW_(I, false, true, D);                                                                 \
-            else if (wt) OHEM_ROW_(I, true, false, MW);                                                                  \
-            else OHEM_ROW_(I, false, false, M);                                                                          \
+            if (gamma) OHEM_ROW_(I, true, false, true, fws, F);                                                          \
+            else if (dsel && wt) OHEM_ROW_(I, true, true, false, wts, DW);                                               \
+            else if (dsel) OHEM_ROW_(I, false, true, false, wts, D);                                                     \
+            else if (wt) OHEM_ROW_(I, true, false, false, wts, MW);                                                      \
+            else OHEM_ROW_(I, false, false, false, wts, M);                                                              \
         } while (0)
-        if (ipl == 1) OHEM_ROW(1, m1, mw1, d1, dw1);
-        else if (ipl == 2) OHEM_ROW(2, m2, mw2, d2, dw2);
-        else OHEM_ROW(4, m4, mw4, d4, dw4);
+        if (ipl == 1) OHEM_ROW(1, m1, mw1, d1, dw1, f1);
+        else if (ipl == 2) OHEM_ROW(2, m2, mw2, d2, dw2, f2);
+        else OHEM_ROW(4, m4, mw4, d4, dw4, f4);
 #undef OHEM_ROW
 #undef OHEM_ROW_
     } else {
         const size_t lds_x = lds + (wt ? OHEM_WT_LDS : 0);  // the segment's buffers stop at 60 KB
-#define OHEM_BWD_(CM, EX, WTV, DSV)                                                                                      \
+#define OHEM_BWD_(CM, EX, WTV, DSV, FLV, FS)                                                                             \
     do {                                                                                                                 \
         if (x8)                                                                                                          \
-            hipLaunchKernelGGL((ohem_up_bwd_x_kernel<CM, EX, 8, WTV, DSV>), dim3(xgrid), dim3(OBX_T), lds_x, stream,     \
+            hipLaunchKernelGGL((ohem_up_bwd_x_kernel<CM, EX, 8, WTV, DSV, FLV>), dim3(xgrid), dim3(OBX_T), lds_x, stream, \
                                hd, labels, nh, B, C, Hl, Wl, H, W, (float)Hl / (float)H, (float)Wl / (float)W, thresh,   \
-                               ignore_lb, coef, SX, nox_max, R, gplane, wts, dsel);                                       \
+                               ignore_lb, coef, SX, nox_max, R, gplane, FS, dsel);                                        \
         else                                                                                                             \
-            hipLaunchKernelGGL((ohem_up_bwd_x_kernel<CM, EX, 0, WTV, DSV>), dim3(xgrid), dim3(OBX_T), lds_x, stream,     \
+            hipLaunchKernelGGL((ohem_up_bwd_x_kernel<CM, EX, 0, WTV, DSV, FLV>), dim3(xgrid), dim3(OBX_T), lds_x, stream, \
                                hd, labels, nh, B, C, Hl, Wl, H, W, (float)Hl / (float)H, (float)Wl / (float)W, thresh,   \
-                               ignore_lb, coef, SX, nox_max, R, gplane, wts, dsel);                                       \
+                               ignore_lb, coef, SX, nox_max, R, gplane, FS, dsel);                                        \
     } while (0)
 #define OHEM_BWD(CM, EX)                                                                                                 \
     do {                                                                                                                 \
-        if (dsel && wt) OHEM_BWD_(CM, EX, true, true);                                                                   \
-        else if (dsel) OHEM_BWD_(CM, EX, false, true);                                                                   \
-        else if (wt) OHEM_BWD_(CM, EX, true, false);                                                                     \
-        else OHEM_BWD_(CM, EX, false, false);                                                                            \
+        if (gamma) OHEM_BWD_(CM, EX, true, false, true, fws);                                                            \
+        else if (dsel && wt) OHEM_BWD_(CM, EX, true, true, false, wts);                                                  \
+        else if (dsel) OHEM_BWD_(CM, EX, false, true, false, wts);                                                       \
+        else if (wt) OHEM_BWD_(CM, EX, true, false, false, wts);                                                         \
+        else OHEM_BWD_(CM, EX, false, false, false, wts);                                                                \
     } while (0)
     if (C == 8) OHEM_BWD(8, true);
     else if (C == 19) OHEM_BWD(19, true);
@@ -980,6 +1106,35 @@ __global__ __launch_bounds__(256) void ohem_stats_kernel(const float* __restrict
 
 hipError_t ohem_stats_run(const float* blk_sum, const int* blk_cnt, int nheads, int nblk, double* stats, hipStream_t stream) {
     hipLaunchKernelGGL(ohem_stats_kernel, dim3(nheads), dim3(256), 0, stream, blk_sum, blk_cnt, nblk, stats);
+    return hipGetLastError();
+}
+
+// The focal forward's partials (blk_sum (nheads,nblk,2) = {sum w_t, sum w_t q^gamma l}, blk_cnt (nheads,nblk)) -> per head
+// [n_valid, D, S] in double: the same walk and the same fixed tree as ohem_stats_kernel (bit-reproducible).
+__global__ __launch_bounds__(256) void focal_stats_kernel(const float* __restrict__ blk_sum, const int* __restrict__ blk_cnt,
+                                                           int nblk, double* __restrict__ stats) {
+    __shared__ long long s_v[256];
+    __shared__ double s_d[256], s_s[256];
+    const int hh = blockIdx.x, t = threadIdx.x;
+    const float2* bs = reinterpret_cast<const float2*>(blk_sum) + (size_t)hh * nblk;
+    const int* bc = blk_cnt + (size_t)hh * nblk;
+    long long nv = 0;
+    double dn = 0.0, sm = 0.0;
+    for (int i = t; i < nblk; i += 256) {
+        const float2 f = bs[i];
+        nv += bc[i], dn += (double)f.x, sm += (double)f.y;
+    }
+    s_v[t] = nv, s_d[t] = dn, s_s[t] = sm;
+    __syncthreads();
+    for (int o = 128; o >= 1; o >>= 1) {
+        if (t < o) s_v[t] += s_v[t + o], s_d[t] += s_d[t + o], s_s[t] += s_s[t + o];
+        __syncthreads();
+    }
+    if (t == 0) stats[3 * hh] = (double)s_v[0], stats[3 * hh + 1] = s_d[0], stats[3 * hh + 2] = s_s[0];
+}
+
+hipError_t focal_stats_run(const float* blk_sum, const int* blk_cnt, int nheads, int nblk, double* stats, hipStream_t stream) {
+    hipLaunchKernelGGL(focal_stats_kernel, dim3(nheads), dim3(256), 0, stream, blk_sum, blk_cnt, nblk, stats);
     return hipGetLastError();
 }
 

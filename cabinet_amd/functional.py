@@ -481,14 +481,14 @@ def ffm_fused(fsp, fcp, conv_w, bn, w1, w2):
 # --------------------------------------------------------------------------- OHEM-CE fused with the final upsample
 
 
-def _class_weight(weight, logits):
+def _class_weight(weight, logits, criterion="OhemCELoss"):
     """A criterion's class-weight buffer as the C ABI wants it: dense fp32 (C,) on the logits' device, or None.  The buffer of
     a criterion under ``.half()`` / AMP may be half precision; no such pointer reaches the library.  A buffer that already is
     fp32, contiguous and on the device is passed as it is (its ADDRESS is what a captured graph replays)."""
     if weight is None:
         return None
     if weight.dim() != 1 or weight.shape[0] != logits.shape[1]:
-        raise RuntimeError(f"OhemCELoss: weight of shape {tuple(weight.shape)} for {logits.shape[1]} classes")
+        raise RuntimeError(f"{criterion}: weight of shape {tuple(weight.shape)} for {logits.shape[1]} classes")
     return _f32c(weight.detach().to(logits.device))
 
 
@@ -726,6 +726,113 @@ class _OhemUpDeviceSelectedPair(torch.autograd.Function):
         scale = (g / sel[:, 2]).to(torch.float32)
         dlow = dlow * scale.view(2, 1, 1, 1, 1)
         return dlow[0], dlow[1], None, None, None, None, None, None, None
+
+
+# ---- softmax focal loss on the same fused operator (reference loss.py:86-127; K19)
+
+
+def focal_up_supported(logits_low, size, gamma):
+    """The fused focal head takes these logits (C <= 32, the LDS row buffers) and this exponent (finite, >= 0)."""
+    import math
+
+    gamma = float(gamma)
+    if not logits_low.is_cuda or logits_low.dim() != 4 or not math.isfinite(gamma) or gamma < 0.0:
+        return False
+    _, C, Hl, Wl = logits_low.shape
+    return bool(_lib.load().cabinet_focal_up_supported(C, Hl, Wl, int(size[0]), int(size[1]), gamma))
+
+
+def focal_up_fwd_hip(lows, labels, size, gammas, ignore_lb, weights=None, out=None):
+    """Focal loss of bilinear_upsample(low -> size) vs labels for one or two heads (``lows``: a list of (B,C,Hl,Wl) tensors of
+    one shape), never materialising the upsample.  Returns loss_px (nh,B,H,W), the UNWEIGHTED per-pixel l = lse - x_label
+    (0 where ignored), and stats (nh,3) float64 = per head [n_valid, D, S] with D = sum w_t, S = sum w_t q^gamma l; n_valid < 0
+    flags a label outside [0, C).  ``out``: an (nh,3) float64 device tensor to write the statistics into.  No host read."""
+    lib = _lib.load()
+    lows, labels = [_f32c(t) for t in lows], _aligned(labels)
+    nh = len(lows)
+    weights = list(weights) if weights is not None else [None] * nh
+    wts = [_class_weight(w, lows[0], "SoftmaxFocalLoss") for w in weights] + [None]
+    gam = [float(g) for g in gammas] + [0.0]
+    B, C, Hl, Wl = lows[0].shape
+    H, W = size
+    dev = lows[0].device
+    nblk = lib.cabinet_ohem_up_blocks(B, H, W)
+    loss_px = torch.empty((nh, B, H, W), dtype=torch.float32, device=dev)
+    blk_sum = torch.empty((nh, nblk, 2), dtype=torch.float32, device=dev)
+    blk_cnt = torch.empty((nh, nblk), dtype=torch.int32, device=dev)
+    stats = out if out is not None else torch.empty((nh, 3), dtype=torch.float64, device=dev)
+    if tuple(stats.shape) != (nh, 3) or stats.dtype != torch.float64 or stats.device != dev or not stats.is_contiguous():
+        raise RuntimeError(f"focal_up_fwd_hip: out must be a contiguous ({nh},3) float64 tensor on {dev}")
+    with torch.cuda.device(dev):
+        rc = lib.cabinet_focal_up_fwd(_ptr(lows[0]), _ptr(lows[1]) if nh == 2 else None, _ptr(labels), B, C, Hl, Wl, H, W,
+                                      gam[0], gam[1], int(ignore_lb), _ptr(loss_px), _ptr(blk_sum), _ptr(blk_cnt),
+                                      _ptr(wts[0]), _ptr(wts[1]), _stream_handle(dev))
+        _lib.check(rc, "cabinet_focal_up_fwd")
+        rc = lib.cabinet_focal_stats(_ptr(blk_sum), _ptr(blk_cnt), nh, nblk, _ptr(stats), _stream_handle(dev))
+    _lib.check(rc, "cabinet_focal_stats")
+    return loss_px, stats
+
+
+def focal_up_bwd_hip(lows, labels, loss_px, size, gammas, ignore_lb, coef, weights=None, out=None):
+    """(nh,B,C,Hl,Wl) = coef * U^T[w_t a(l) (softmax - onehot)] from the forward's ``loss_px`` (see focal_up_fwd_hip: the same
+    gammas and weights).  ``out``: a buffer of that shape; every element is written."""
+    lib = _lib.load()
+    lows, labels, loss_px = [_f32c(t) for t in lows], _aligned(labels), _f32c(loss_px)
+    nh = len(lows)
+    weights = list(weights) if weights is not None else [None] * nh
+    wts = [_class_weight(w, lows[0], "SoftmaxFocalLoss") for w in weights] + [None]
+    gam = [float(g) for g in gammas] + [0.0]
+    B, C, Hl, Wl = lows[0].shape
+    H, W = size
+    dev = lows[0].device
+    dlow = out if out is not None else torch.empty((nh, B, C, Hl, Wl), dtype=torch.float32, device=dev)
+    if tuple(dlow.shape) != (nh, B, C, Hl, Wl) or dlow.dtype != torch.float32 or dlow.device != dev \
+            or not dlow.is_contiguous() or dlow.data_ptr() & 15:
+        raise RuntimeError(f"focal_up_bwd_hip: out must be a contiguous, 16-byte aligned ({nh},{B},{C},{Hl},{Wl}) float32 "
+                           f"tensor on {dev}")
+    ws, nbytes = _workspace(lib.cabinet_focal_up_bwd_workspace_bytes(nh, B, C, Hl, Wl, H, W), dev)
+    with torch.cuda.device(dev):
+        rc = lib.cabinet_focal_up_bwd(_ptr(lows[0]), _ptr(lows[1]) if nh == 2 else None, _ptr(labels), _ptr(loss_px), B, C, Hl,
+                                      Wl, H, W, gam[0], gam[1], int(ignore_lb), float(coef), _ptr(dlow), _ptr(ws), nbytes,
+                                      _ptr(wts[0]), _ptr(wts[1]), _stream_handle(dev))
+    _lib.check(rc, "cabinet_focal_up_bwd")
+    return dlow
+
+
+class _FocalUp(torch.autograd.Function):
+    """Sum over one or two heads of SoftmaxFocalLoss behind the upsample: loss = sum_heads S / D.  The reference's semantics,
+    all on the device: no valid pixel (or only classes of weight 0) -> NaN (0 / 0) and a gradient of exactly 0; a label out of
+    range -> NaN (``stats[:, 0] < 0`` says why).  Nothing is read on the host and nothing data-dependent is a kernel argument:
+    replayable from a captured hipGraph whatever the batch.  ``stats_out``: where the (nh,3) statistics go (a static tensor of
+    a graphed step)."""
+
+    @staticmethod
+    def forward(fn_ctx, labels, size, ignore_lb, gammas, weights, stats_out, *lows):
+        loss_px, stats = focal_up_fwd_hip([t.detach() for t in lows], labels, size, gammas, ignore_lb, weights, out=stats_out)
+        fn_ctx.save_for_backward(labels, loss_px, stats, *lows)
+        fn_ctx.meta = (size, ignore_lb, tuple(gammas))
+        fn_ctx.weights = tuple(weights)  # not through save_for_backward: an in-place update of the buffer is no autograd error
+        per_head = torch.where(stats[:, 0] < 0, torch.full_like(stats[:, 2], float("nan")), stats[:, 2] / stats[:, 1])
+        return per_head.sum().to(torch.float32)
+
+    @staticmethod
+    def backward(fn_ctx, g):
+        labels, loss_px, stats, *lows = fn_ctx.saved_tensors
+        size, ignore_lb, gammas = fn_ctx.meta
+        dlow = focal_up_bwd_hip(lows, labels, loss_px, size, gammas, ignore_lb, 1.0, fn_ctx.weights)
+        D = stats[:, 1]
+        scale = torch.where(D > 0, g / D, torch.zeros_like(D)).to(torch.float32)  # upstream gradient and 1 / D: device scalars
+        dlow = dlow * scale.view(-1, 1, 1, 1, 1)
+        return (None,) * 6 + tuple(dlow[i] for i in range(len(lows)))
+
+
+def focal_up_loss(lows, labels, size, gammas, ignore_lb, weights=None, stats_out=None):
+    """``sum_i SoftmaxFocalLoss(gammas[i], weights[i], ignore_lb)(interpolate(lows[i], size), labels)`` on the fused kernels; one
+    or two heads of one shape, ONE forward launch and ONE backward launch pair."""
+    lows = [_f32c(t) for t in lows]
+    weights = list(weights) if weights is not None else [None] * len(lows)
+    return _FocalUp.apply(_aligned(labels), tuple(int(s) for s in size), int(ignore_lb), tuple(float(g) for g in gammas),
+                          tuple(weights), stats_out, *lows)
 
 
 # --------------------------------------------------------------------------- CAB local branch + block output (K5)

@@ -122,7 +122,8 @@ class OhemCELoss(nn.Module):
 
 class SoftmaxFocalLoss(nn.Module):
     """Focal loss on softmax probabilities with optional per-class weights -- mirror of reference
-    ``src/utils/loss.py:86-128`` (API parity of ``src.utils.loss``; not on the timed path: train.py builds OhemCELoss)."""
+    ``src/utils/loss.py:86-128``.  ``forward`` is the composite; ``forward_upsampled`` runs the criterion behind the final
+    upsample on the fused kernels (the focal mode of the OHEM head)."""
 
     def __init__(self, gamma, weight=None, ignore_lb=255):
         super().__init__()
@@ -137,6 +138,67 @@ class SoftmaxFocalLoss(nn.Module):
         focal = (1 - log_prob.exp()) ** self.gamma * log_prob
         w = self.weight if isinstance(self.weight, torch.Tensor) else None
         return F.nll_loss(focal, labels, weight=w, ignore_index=self.ignore_lb)
+
+    def _class_weight(self):
+        return self.weight if isinstance(self.weight, torch.Tensor) else None
+
+    def _fused(self, logits_low, size):
+        """The fused head takes this call: HIP logits, <= 32 classes inside the kernels' row buffers, a finite gamma >= 0."""
+        if not (logits_low.is_cuda and logits_low.dim() == 4 and logits_low.shape[1] <= 32):
+            return False
+        from .functional import focal_up_supported
+
+        return focal_up_supported(logits_low, size, self.gamma)
+
+    def forward_upsampled(self, logits_low, labels, size=None):
+        """``self(F.interpolate(logits_low, size, mode="bilinear", align_corners=False), labels)`` with the upsample, the
+        softmax and the focal factor fused into hand-written kernels on HIP tensors (``cabinet_focal_up_fwd/bwd``): neither the
+        (B,C,H,W) logits nor their log-softmax, powers or per-pixel gradient are materialised, and nothing is read on the host.
+        No valid pixel, or only classes of weight 0: NaN (0 / 0) with a gradient of exactly 0; a label outside [0, C) that is
+        not ``ignore_lb``: NaN.  Where the composite's autograd returns NaN gradients the fused head returns 0: for
+        0 < gamma < 1 at a pixel with q = 1 - p_t = 0 in fp32 (0^(gamma-1) * 0), and for valid pixels whose classes all weigh 0
+        (0 / 0 in nll_loss's backward).  CPU tensors, more than 32 classes and a negative or non-finite gamma take the
+        composite path."""
+        size = tuple(size) if size is not None else tuple(labels.shape[-2:])
+        if not self._fused(logits_low, size):
+            return self.forward(F.interpolate(logits_low, size=size, mode="bilinear", align_corners=False), labels)
+        from .functional import focal_up_loss
+
+        _check_upsampled_labels("SoftmaxFocalLoss", logits_low, labels, size)
+        return focal_up_loss([logits_low], labels, size, [self.gamma], self.ignore_lb, [self._class_weight()])
+
+    def extra_repr(self):
+        return f"gamma={self.gamma}, ignore_lb={self.ignore_lb}"
+
+
+def _check_upsampled_labels(name, logits_low, labels, size):
+    # the kernels read `const long long*` labels of exactly (B,H,W): anything else is the caller's error, as it is
+    # for F.cross_entropy ("expected scalar type Long"), never a silent reinterpretation of the bytes
+    if labels.dtype != torch.int64:
+        raise RuntimeError(f"{name}.forward_upsampled: labels must be int64 (torch.long), got {labels.dtype}")
+    if tuple(labels.shape) != (logits_low.shape[0],) + tuple(size) or labels.device != logits_low.device:
+        raise RuntimeError(f"{name}.forward_upsampled: labels {tuple(labels.shape)} on {labels.device} do not "
+                           f"match logits batch {logits_low.shape[0]} x size {tuple(size)} on {logits_low.device}")
+
+
+def focal_upsampled_pair(crit_a, low_a, crit_b, low_b, labels, size, stats_out=None):
+    """``crit_a.forward_upsampled(low_a, ...) + crit_b.forward_upsampled(low_b, ...)`` for two SoftmaxFocalLoss: ONE forward
+    launch and ONE backward launch pair when the heads agree in shape and ignore label (gamma and class weights are per
+    head), else the sum of the per-head calls.  ``stats_out``: a (2,3) float64 device tensor that receives per head
+    [n_valid, D, S] of the one-launch form (a graphed step's static tensor)."""
+    size = tuple(size) if size is not None else tuple(labels.shape[-2:])
+    same = (low_a.is_cuda and low_b.is_cuda and low_a.shape == low_b.shape and low_a.device == low_b.device
+            and crit_a.ignore_lb == crit_b.ignore_lb and crit_a._fused(low_a, size) and crit_b._fused(low_b, size))
+    if not same:
+        if stats_out is not None:
+            raise RuntimeError("focal_upsampled_pair: `stats_out` needs the one-launch pair (two fused heads of one shape and "
+                               "ignore label)")
+        return crit_a.forward_upsampled(low_a, labels, size) + crit_b.forward_upsampled(low_b, labels, size)
+    from .functional import focal_up_loss
+
+    _check_upsampled_labels("SoftmaxFocalLoss", low_a, labels, size)
+    return focal_up_loss([low_a, low_b], labels, size, [crit_a.gamma, crit_b.gamma], crit_a.ignore_lb,
+                         [crit_a._class_weight(), crit_b._class_weight()], stats_out=stats_out)
 
 
 class _PairPrep:
@@ -251,3 +313,14 @@ def ohem_upsampled_pair(crit_a, low_a, crit_b, low_b, labels, size):
     prep = fused_pair_launch(crit_a, low_a, crit_b, low_b, labels, size)
     stats = prep.stats
     return fused_pair_finish(prep, stats.tolist() if stats is not None else None)
+
+
+def upsampled_pair(crit_a, low_a, crit_b, low_b, labels, size):
+    """The step's loss, ``crit_a.forward_upsampled(low_a, ...) + crit_b.forward_upsampled(low_b, ...)``, on the paired kernels
+    of the criteria's kind: two OhemCELoss -> ohem_upsampled_pair, two SoftmaxFocalLoss -> focal_upsampled_pair, anything
+    else -> the sum of the per-head calls."""
+    if isinstance(crit_a, OhemCELoss) and isinstance(crit_b, OhemCELoss):
+        return ohem_upsampled_pair(crit_a, low_a, crit_b, low_b, labels, size)
+    if isinstance(crit_a, SoftmaxFocalLoss) and isinstance(crit_b, SoftmaxFocalLoss):
+        return focal_upsampled_pair(crit_a, low_a, crit_b, low_b, labels, size)
+    return crit_a.forward_upsampled(low_a, labels, size) + crit_b.forward_upsampled(low_b, labels, size)

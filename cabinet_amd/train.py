@@ -21,7 +21,7 @@ import os
 
 import torch
 
-from .loss import OhemCELoss, fused_pair_finish, fused_pair_launch, ohem_upsampled_pair
+from .loss import OhemCELoss, SoftmaxFocalLoss, focal_upsampled_pair, fused_pair_finish, fused_pair_launch, upsampled_pair
 from .models.cabinet import CABiNet
 from .models.constants import DEFAULT_IGNORE_LABEL, DEFAULT_SCORE_THRESHOLD, MOBILENETV3_CFGS, OHEM_DIVISOR
 
@@ -52,10 +52,16 @@ def build_model(mode="large", n_classes=8, device="cpu", seed=0, gamma=None, fre
 
 
 def make_criteria(batch, height, width, device, thresh=DEFAULT_SCORE_THRESHOLD, ignore=DEFAULT_IGNORE_LABEL, weight=None,
-                  device_select=False):
+                  device_select=False, loss="ohem", gamma=2.0):
     """The step's two criteria.  ``weight``: per-class weights (a tensor or a sequence of ``n_classes`` floats), handed to both
     criteria as the reference does (train.py:344-349); each criterion registers its own fp32 copy as a buffer.
-    ``device_select``: see OhemCELoss (the top-n_min branch on the HIP kernels)."""
+    ``device_select``: see OhemCELoss (the top-n_min branch on the HIP kernels).
+    ``loss``: ``"ohem"`` (two OhemCELoss) or ``"focal"`` (two ``SoftmaxFocalLoss(gamma, weight, ignore)``)."""
+    if loss == "focal":
+        w = None if weight is None else torch.as_tensor(weight, dtype=torch.float32).detach()
+        return tuple(SoftmaxFocalLoss(gamma, None if w is None else w.clone(), ignore).to(device) for _ in range(2))
+    if loss != "ohem":
+        raise ValueError(f"make_criteria: loss={loss!r} (\"ohem\" or \"focal\")")
     n_min = max(1, batch * height * width // OHEM_DIVISOR)
     if weight is not None:
         weight = torch.as_tensor(weight, dtype=torch.float32).detach()
@@ -126,7 +132,7 @@ class TrainStep:
                 if fused:
                     low, low16 = self.net.forward_lowres(im)
                     size = im.shape[2:]
-                    loss = ohem_upsampled_pair(self.crit_p, low, self.crit_16, low16, lb, size)
+                    loss = upsampled_pair(self.crit_p, low, self.crit_16, low16, lb, size)
                 else:
                     out, out16 = self.net(im)
                     loss = self.crit_p(out, lb) + self.crit_16(out16, lb)
@@ -257,13 +263,25 @@ class GraphedTrainStep:
     still serves the step with both heads on that branch, bit for bit; ``fallbacks`` then counts all-ignored batches only,
     and the capture batch may be on either branch (recording executes nothing).  B-any's backward leaves its gradients in
     tensors of its own and ends with one multi-tensor copy into graph B's static gradient tensors, so ``.grad`` and a
-    captured optimizer step read the same addresses after either graph."""
+    captured optimizer step read the same addresses after either graph.
+
+    Two ``SoftmaxFocalLoss`` criteria (``make_criteria(loss="focal")``) take a third form, ONE graph: focal has no
+    data-dependent branch, so forward + fused pair (``focal_upsampled_pair``) + loss + backward are recorded together, followed
+    by the optimizer segment as above.  There is no BatchNorm snapshot, no host read and no eager fallback: ``fallbacks`` stays
+    0 whatever the labels, an all-ignored batch replays like any other (NaN loss, gradients exactly 0, as the eager step), and
+    ``last_stats`` is the static (2,3) float64 device tensor ``[n_valid, D, S]`` per head of the last replay (``n_valid < 0``:
+    a label out of range).  ``g_bwd`` stays None; ``device_select`` is refused (there is no branch to select)."""
 
     def __init__(self, net, criteria, optimizer=None, warmup=2, capture_optimizer=False, before_optimizer=None,
                  device_select=False):
         self.net, (self.crit_p, self.crit_16) = net, criteria
         self.optimizer, self.warmup = optimizer, warmup
         self.device_select = bool(device_select)
+        # two focal criteria: ONE graph (forward + fused pair + loss + backward), see _capture_focal
+        self.focal = isinstance(self.crit_p, SoftmaxFocalLoss) and isinstance(self.crit_16, SoftmaxFocalLoss)
+        if self.focal and self.device_select:
+            raise RuntimeError("GraphedTrainStep: device_select is an OHEM option; focal criteria have no branch to select")
+        self.last_stats = None  # focal: the static (2,3) device tensor [n_valid, D, S] per head of the last replay
         if self.device_select:
             self.crit_p.device_select = self.crit_16.device_select = True  # the warm-up and all-ignored steps run eagerly
         self.opt_seg = _OptimizerSegment(optimizer, capture_optimizer, before_optimizer)
@@ -271,9 +289,38 @@ class GraphedTrainStep:
         self.g_fwd = self.g_bwd = self.g_any = None
         self.fallbacks = self.device_selected = self._calls = 0  # eager fallbacks / replays of graph B-any
 
+    def _capture_focal(self, im, lb):
+        """Focal criteria have no data-dependent branch: forward, the fused pair, the loss and the backward are ONE graph.
+        No BatchNorm snapshot, no host read, no eager fallback: an all-ignored batch replays like any other (loss NaN,
+        gradients exactly 0, as the eager step)."""
+        self.s_im, self.s_lb = im.clone(), lb.clone()
+        eager_grads = {p: p.grad for p in self.net.parameters() if p.grad is not None}
+        for p in self.net.parameters():
+            p.grad = None
+        size = tuple(im.shape[2:])
+        self.last_stats = torch.zeros((2, 3), dtype=torch.float64, device=im.device)
+        torch.cuda.synchronize()
+        self.g_fwd = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(self.g_fwd, capture_error_mode=_CAPTURE_MODE):
+            low, low16 = self.net.forward_lowres(self.s_im)
+            loss = focal_upsampled_pair(self.crit_p, low, self.crit_16, low16, self.s_lb, size, stats_out=self.last_stats)
+            loss.backward()
+            self.s_loss = loss.detach()
+        self.s_grads = [(p, p.grad) for p in self.net.parameters() if p.grad is not None]
+        self.opt_seg.record(self.g_fwd.pool())
+        with torch.no_grad():
+            for p, g in self.s_grads:
+                if p in eager_grads:
+                    g.copy_(eager_grads[p])
+                else:
+                    g.zero_()
+        torch.cuda.synchronize()
+
     def _capture(self, im, lb):
         """Record the two graphs on this batch.  Nothing of the step executes here (capture only records), except one
         replay of graph A to learn the batch's OHEM branch, whose BatchNorm side effects are undone."""
+        if self.focal:
+            return self._capture_focal(im, lb)
         self.s_im, self.s_lb = im.clone(), lb.clone()
         self.snap = _BufferSnapshot(self.net)
         # the gradients of the eager step that just ran: the static tensors bound below have only been RECORDED into, never
@@ -369,6 +416,12 @@ class GraphedTrainStep:
         _check_static_shapes(self, im, lb)
         self.s_im.copy_(im, non_blocking=True)
         self.s_lb.copy_(lb, non_blocking=True)
+        if self.focal:  # one graph, nothing read on the host
+            for p, g in self.s_grads:
+                p.grad = g
+            self.g_fwd.replay()
+            self.opt_seg.run()
+            return self.s_loss
         self.snap.save()
         self.g_fwd.replay()
         host = self.s_stats.tolist()  # the step's one host sync
@@ -487,6 +540,10 @@ class GraphedDDPStep:
         self.opt_seg = _OptimizerSegment(optimizer, capture_optimizer, before_optimizer)
         dev = next(net.parameters()).device
         self.use_graphs = (dev.type == "cuda") if use_graphs is None else bool(use_graphs)
+        self._ohem = isinstance(self.crit_p, OhemCELoss) and isinstance(self.crit_16, OhemCELoss)
+        if self.use_graphs and not self._ohem:
+            raise RuntimeError("GraphedDDPStep with graphs needs two OhemCELoss criteria: its graph segments are cut around the "
+                               "OHEM branch read; focal criteria run with use_graphs=False (or in GraphedTrainStep, one graph)")
         dec, mid, last = [], [], []
         for name, child in net.named_children():
             for p in child.parameters():
@@ -549,6 +606,9 @@ class GraphedDDPStep:
     def _forward(self, im, lb):
         """-> ((pair prep, its device statistics) | None, loss | None, boundary tensors [sb output, mobile output])"""
         boundary = []
+        if im.is_cuda and not self._ohem:
+            low, low16 = self.net.forward_lowres(im, boundary)
+            return None, upsampled_pair(self.crit_p, low, self.crit_16, low16, lb, tuple(im.shape[2:])), boundary
         if im.is_cuda:
             low, low16 = self.net.forward_lowres(im, boundary)
             prep = fused_pair_launch(self.crit_p, low, self.crit_16, low16, lb, tuple(im.shape[2:]))

@@ -274,6 +274,40 @@ int cabinet_ohem_up_pair_w_bwd_sel(const float* logits_low_a, const float* logit
                                    int ignore_lb, float coef, float* dlogits_low, void* workspace, size_t workspace_bytes,
                                    const float* class_weight_a, const float* class_weight_b, cabinet_stream_t stream);
 
+/* Softmax focal loss behind the same fused upsample -- reference src/utils/loss.py:86-127 (SoftmaxFocalLoss) on the output of
+ * cabinet.py:240-245; the focal mode of the OHEM kernels above.  (Added under ABI v8.)  Every entry point takes one or two heads
+ * over the same labels: logits_low_b == NULL means one (gamma_b, class_weight_b are then unused); with two, loss_px is
+ * (2,B,H,W), blk_sum (2,nblk,2), blk_cnt (2,nblk), dlogits_low (2,B,C,Hl,Wl), nblk = cabinet_ohem_up_blocks(B,H,W).
+ * Per valid pixel (label != ignore_lb), with z the low logits, U the bilinear upsample (align_corners=False), t the label:
+ *   l = lse(Uz) - (Uz)_t,  p = exp(-l),  q = 1 - p
+ * and per head, w the class weights (NULL = ones; non-negative, finite):
+ *   D = sum w_t,  S = sum w_t q^gamma l,  loss = S / D,
+ *   a = q^gamma + gamma p q^(gamma-1) l  ( = q^(gamma-1) (q + gamma p l) >= 0 ),
+ *   dloss/dz = (g / D) U^T[ w_t a (softmax - onehot) ].
+ * Pinned values: q is formed as -expm1(-l), never as 1 - exp(-l); q^0 = 1 also at q = 0 (torch's 0 ** 0); for gamma > 0 and
+ * q = 0 the pixel's term and a are 0 -- also for 0 < gamma < 1, where the reference's fp32 autograd returns NaN gradients
+ * (0^(gamma-1) * 0); q^(gamma-1) is never formed on its own.  gamma is a run-time value per head: finite and >= 0.
+ * cabinet_focal_up_supported: 1, or 0 with the reason in cabinet_last_error() (the limits of the OHEM head: C <= 32, the LDS
+ *   row buffers; and gamma).
+ * cabinet_focal_up_fwd: loss_px = the UNWEIGHTED l (0 at ignored pixels), and per workgroup, ordered:
+ *   blk_sum[blk] = {sum w_t, sum w_t q^gamma l}, blk_cnt[blk] = #valid, or -2^30 when the block met a label outside [0,C)
+ *   that is not ignore_lb (such a label is clamped before it indexes anything).
+ * cabinet_focal_stats: partials -> stats (nheads,3) double = [n_valid, D, S], fixed summation order; n_valid < 0 = bad label.
+ * cabinet_focal_up_bwd: dlogits_low = coef * U^T[ w_t a(loss_px) (softmax - onehot) ] from the forward's loss_px and the same
+ *   gamma / weights; a pixel whose factor is 0 is switched off.  The caller folds upstream_grad / D in.  No atomics, ordered
+ *   sums: bit-reproducible.  Workspace: cabinet_focal_up_bwd_workspace_bytes(nheads, ...). */
+int cabinet_focal_up_supported(int C, int Hl, int Wl, int H, int W, float gamma);
+int cabinet_focal_up_fwd(const float* logits_low_a, const float* logits_low_b, const long long* labels,
+                         int B, int C, int Hl, int Wl, int H, int W, float gamma_a, float gamma_b, int ignore_lb,
+                         float* loss_px, float* blk_sum, int* blk_cnt,
+                         const float* class_weight_a, const float* class_weight_b, cabinet_stream_t stream);
+int cabinet_focal_stats(const float* blk_sum, const int* blk_cnt, int nheads, int nblk, double* stats, cabinet_stream_t stream);
+size_t cabinet_focal_up_bwd_workspace_bytes(int nheads, int B, int C, int Hl, int Wl, int H, int W);
+int cabinet_focal_up_bwd(const float* logits_low_a, const float* logits_low_b, const long long* labels,
+                         const float* loss_px, int B, int C, int Hl, int Wl, int H, int W, float gamma_a, float gamma_b,
+                         int ignore_lb, float coef, float* dlogits_low, void* workspace, size_t workspace_bytes,
+                         const float* class_weight_a, const float* class_weight_b, cabinet_stream_t stream);
+
 /* ------------------------------------------------------------------------- *
  * CAB local branch + block output.
  * Replaces src/models/cab.py:175-184 (LocalAttention.forward: three DWConv = depthwise 3x3 conv (cab.py:36-45)
