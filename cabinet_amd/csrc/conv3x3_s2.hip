@@ -7,13 +7,21 @@
 //     dW[co][ci][ky][kx] = sum_{b,oy,ox} dY[b][co][oy][ox] * X[b][ci][2 oy - 1 + ky][2 ox - 1 + kx]
 // contracts over pixels, the contiguous axis of BOTH operands in NCHW.  The forward stays the stock operator's.
 //
-//   64 -> 64 : a workgroup (4 waves) walks output rows oy of one 32-pixel column tile.  Per row it stages the 64 x 32 dy
-//              segment ([co][33]) and the 64 x 3 x 65 input patch ([ci][3][65]: plane pitch 195, odd, so the 32 channels on
-//              32 lanes fall on 32 banks) in LDS.  dW is 2 x 2 x 9 blocks of 32 x 32 (co half, ci half, tap); wave (i, j) owns
-//              the nine taps of its (co half, ci half): 144 accumulator registers, one A read and nine B reads ("pixel pair
-//              on h, channel on li") per nine exact-fp32 MFMA 32x32x2.  All four waves walk the same pixels and own disjoint
-//              blocks, so no cross-wave sum exists: each wave stores its blocks of the workgroup's slab.  58 KB of LDS: two
-//              workgroups per CU, one stages while the other multiplies.
+//   64 -> 64 : a workgroup (4 waves) walks output rows oy of one 32-pixel column tile.  Per row it multiplies the 64 x 32 dy
+//              segment ([co][33]) and the 64 x 3 x 65 input patch ([ci][3 slots][65]: channel pitch 195, odd, so the 32
+//              channels on 32 lanes fall on 32 banks) out of LDS.  dW is 2 x 2 x 9 blocks of 32 x 32 (co half, ci half, tap);
+//              wave (i, j) owns the nine taps of its (co half, ci half): 144 accumulator registers, one A read and nine B
+//              reads ("pixel pair on h, channel on li") per nine exact-fp32 MFMA 32x32x2.  All four waves walk the same pixels
+//              and own disjoint blocks, so no cross-wave sum exists: each wave stores its blocks of the workgroup's slab.
+//              Staging: the three patch rows are a ring -- input row 2 oy + 1 of step oy is row 2 (oy + 1) - 1 of the next step
+//              and stays in its slot; the two new rows and the dy segment of step oy + 1 are requested before the MFMAs of
+//              step oy (41 registers per thread: whole-wave row segments at wave-uniform (channel, row) bases, lane = column,
+//              unconditional clamped loads) and written behind them, 0 selected on the way into LDS for iy = -1, iy >= H,
+//              ix = -1, ix >= W and ox >= Wo.  Every input row is fetched once per workgroup.  Two barriers per step: a
+//              one-barrier ring needs five row slots (100 KB); with three, 58 KB of LDS and 246 VGPRs keep two workgroups
+//              per CU.  The staging this replaces (57 scalar loads per thread and step, each behind a division and a bounds
+//              test, all written to LDS before the step's first MFMA, the shared row read again) ran at 0.21 / 0.18 of the
+//              fp32 MFMA rate (sb.conv2 / sb.conv3, config 3); this one at 0.63 / 0.48, with the same bits.
 //   3 -> 16  : K9's weight-gradient form at (Ci 3, k 3, Co 16): a 4 x 32 output tile, the dy tile ([32][129], rows 16..31
 //              zero) and the 3 x 9 x 65 patch in LDS, one 32 x 32 block per wave (27 of 32 columns live), wave = tile row,
 //              ordered cross-wave sum.  234 MB of operands for 1.8 GFLOP: a streaming kernel.
@@ -72,13 +80,20 @@ static C3Plan cw_plan(const C3Shape& s) {
     return p;
 }
 
+// load at a wave-uniform base + a 32-bit per-lane byte offset
+__device__ __forceinline__ float cd_ld(const float* base, unsigned byte_off) {
+    return *reinterpret_cast<const float*>(reinterpret_cast<const char*>(base) + byte_off);
+}
+
+constexpr int CW_PR = CW_C / 4;  // 16 channels' row segments per wave and input row
+
 __global__ __launch_bounds__(256, 2) void conv3x3s2_wgrad64_kernel(const float* __restrict__ dy, const float* __restrict__ x,
                                                                  C3Shape s, int tiles_x, int strips, int rows_per,
                                                                  float* __restrict__ slabs) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
-    float* xs = smem;                 // [64][3][65]
+    float* xs = smem;                 // [64][3 slots][65]: a ring of input rows; column 0 is ix0 = 2 ox0 - 1
     float* dys = xs + CW_C * CW_XP;   // [64][33]
-    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, li = lane & 31, h = lane >> 5;
+    const int tid = threadIdx.x, wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63, li = lane & 31, h = lane >> 5;
     int bi = blockIdx.x;
     const int tx = bi % tiles_x;
     bi /= tiles_x;
@@ -97,28 +112,81 @@ __global__ __launch_bounds__(256, 2) void conv3x3s2_wgrad64_kernel(const float* 
     const float* dyb = dy + (size_t)b * CW_C * s.Ho * s.Wo;
     const float* arow = dys + (32 * ch + li) * CW_DLD + h;
     const float* brow = xs + (32 * cj + li) * CW_XP + 2 * h;
+    // Staging.  An input row is 64 channels x 65 columns: this wave's 16 channels as row segments (wave-uniform (ci, row) base,
+    // lane = column 2 ox0 + lane, patch column 1 + lane) and the left halo column ix0 as one element per thread (thread = (row of
+    // the request, channel)).  The dy segment is 64 channels x 32 columns: a wave load takes two channels (co = 16 wave + 2 j + h,
+    // column ox0 + li).  Every load is unconditional: row and column are clamped into the tensor, and what lies outside it
+    // (iy = -1, iy >= H, ix = -1, ix >= W, ox >= Wo) is replaced by 0 on the way into LDS.
+    const unsigned colo = (unsigned)min(2 * ox0 + lane, s.W - 1) * 4u;
+    const bool col_ok = 2 * ox0 + lane < s.W, halo_ok = ix0 >= 0, dcol_ok = ox0 + li < s.Wo;
+    const int hrow = tid >> 6, hch = tid & 63;
+    const float* dyl = dyb + (size_t)h * s.Ho * s.Wo + min(ox0 + li, s.Wo - 1);
+    float xr[2 * CW_PR], xh, dr[CW_PR / 2];
+    // rows iya (and, nr = 2, iyb) of x; with_dy: the dy segment of output row oy
+    auto request = [&](int nr, int iya, int iyb, bool with_dy, int oy) {
+        const int ya = min(max(iya, 0), s.H - 1), yb = min(max(iyb, 0), s.H - 1);
+#pragma unroll
+        for (int j = 0; j < CW_PR; ++j) xr[j] = cd_ld(xb + ((size_t)(CW_PR * wave + j) * s.H + ya) * s.W, colo);
+        if (nr == 2) {
+#pragma unroll
+            for (int j = 0; j < CW_PR; ++j) xr[CW_PR + j] = cd_ld(xb + ((size_t)(CW_PR * wave + j) * s.H + yb) * s.W, colo);
+        }
+        xh = xb[((size_t)hch * s.H + (hrow == 0 ? ya : yb)) * s.W + max(ix0, 0)];
+        if (with_dy) {
+#pragma unroll
+            for (int j = 0; j < CW_PR / 2; ++j) dr[j] = dyl[((size_t)(CW_PR * wave + 2 * j) * s.Ho + oy) * s.Wo];
+        }
+    };
+    auto commit = [&](int nr, int iya, int iyb, int sa, int sb, bool with_dy) {
+        const bool oka = iya >= 0 && iya < s.H, okb = iyb >= 0 && iyb < s.H;
+        float* d = xs + CW_PR * wave * CW_XP + 1 + lane;
+#pragma unroll
+        for (int j = 0; j < CW_PR; ++j) d[j * CW_XP + sa * CW_IW] = (oka && col_ok) ? xr[j] : 0.f;
+        if (nr == 2) {
+#pragma unroll
+            for (int j = 0; j < CW_PR; ++j) d[j * CW_XP + sb * CW_IW] = (okb && col_ok) ? xr[CW_PR + j] : 0.f;
+        }
+        if (hrow < nr) xs[hch * CW_XP + (hrow == 0 ? sa : sb) * CW_IW] = ((hrow == 0 ? oka : okb) && halo_ok) ? xh : 0.f;
+        if (with_dy) {
+#pragma unroll
+            for (int j = 0; j < CW_PR / 2; ++j) dys[(CW_PR * wave + 2 * j + h) * CW_DLD + li] = dcol_ok ? dr[j] : 0.f;
+        }
+    };
+    // Input row iy of the strip lives in slot (iy - iy_begin) % 3.  Step oy multiplies rows 2 oy - 1 .. 2 oy + 1 (slots s0, s0 + 1,
+    // s0 + 2) while the two new rows of step oy + 1 and its dy segment are in flight in registers; behind the MFMAs they are
+    // written over rows 2 oy - 1 and 2 oy, and row 2 oy + 1 stays where it is: every input row is fetched once per workgroup.
+    // Five slots (three in use, two being written) would take one barrier per step and 100 KB; three take two and 58 KB, and
+    // two workgroups share a CU.
+    const int iy_begin = 2 * oy_begin - 1;
+    request(2, iy_begin, iy_begin + 1, true, oy_begin);
+    commit(2, iy_begin, iy_begin + 1, 0, 1, true);
+    request(1, iy_begin + 2, iy_begin + 2, false, 0);
+    commit(1, iy_begin + 2, iy_begin + 2, 2, 2, false);
+    __syncthreads();
+    int s0 = 0;  // slot of row 2 oy - 1
     for (int oy = oy_begin; oy < oy_end; ++oy) {
-        const int iy0 = 2 * oy - 1;
-        __syncthreads();  // the previous row's operand reads are done
-        for (int i = tid; i < CW_C * CW_XP; i += 256) {
-            const int ci = i / CW_XP, r = i - ci * CW_XP, yy = r / CW_IW, xx = r - yy * CW_IW;
-            const int iy = iy0 + yy, ix = ix0 + xx;
-            xs[i] = (iy >= 0 && iy < s.H && ix >= 0 && ix < s.W) ? xb[((size_t)ci * s.H + iy) * s.W + ix] : 0.f;
-        }
-        for (int i = tid; i < CW_C * CW_TW; i += 256) {
-            const int co = i >> 5, c = i & 31, ox = ox0 + c;
-            dys[co * CW_DLD + c] = ox < s.Wo ? dyb[((size_t)co * s.Ho + oy) * s.Wo + ox] : 0.f;
-        }
-        __syncthreads();
+        const int s1 = s0 == 2 ? 0 : s0 + 1, s2 = s1 == 2 ? 0 : s1 + 1;
+        const bool more = oy + 1 < oy_end;
+        if (more) request(2, 2 * oy + 2, 2 * oy + 3, true, oy + 1);  // in flight underneath this step's MFMAs
+        const float* b0 = brow + s0 * CW_IW;
+        const float* b1 = brow + s1 * CW_IW;
+        const float* b2 = brow + s2 * CW_IW;
 #pragma unroll
         for (int c0 = 0; c0 < CW_TW; c0 += 2) {  // pixels c0 + h: two per MFMA
             const float a = arow[c0];
 #pragma unroll
-            for (int ky = 0; ky < 3; ++ky)
+            for (int kx = 0; kx < 3; ++kx) acc[kx] = mfma32(a, b0[2 * c0 + kx], acc[kx]);
 #pragma unroll
-                for (int kx = 0; kx < 3; ++kx)
-                    acc[3 * ky + kx] = mfma32(a, brow[ky * CW_IW + 2 * c0 + kx], acc[3 * ky + kx]);
+            for (int kx = 0; kx < 3; ++kx) acc[3 + kx] = mfma32(a, b1[2 * c0 + kx], acc[3 + kx]);
+#pragma unroll
+            for (int kx = 0; kx < 3; ++kx) acc[6 + kx] = mfma32(a, b2[2 * c0 + kx], acc[6 + kx]);
         }
+        if (more) {
+            __syncthreads();  // every wave has read this step's operands
+            commit(2, 2 * oy + 2, 2 * oy + 3, s0, s1, true);
+            __syncthreads();
+        }
+        s0 = s2;
     }
     // this wave's 32 x 32 x 9 part of the slab, in dW's own layout [co][ci][tap]
     float* slab = slabs + (size_t)blockIdx.x * CW_SLAB;
@@ -202,11 +270,6 @@ constexpr int CD_RP = 80;             // row pitch of the dy ring (65 columns li
 constexpr int CD_SLOTS = 3;           // rows m, m + 1 of the step and row m + 2 on its way in
 constexpr int CD_CP = CD_SLOTS * CD_RP;  // 240: channel pitch, = 16 mod 32 (the two channels of a 32-lane read group: disjoint banks)
 constexpr int CD_PR = CW_C / 4;       // 16 channels' row segments per wave and dy row
-
-// load at a wave-uniform base + a 32-bit per-lane byte offset
-__device__ __forceinline__ float cd_ld(const float* base, unsigned byte_off) {
-    return *reinterpret_cast<const float*>(reinterpret_cast<const char*>(base) + byte_off);
-}
 
 // the tap of dY that input parity 0 (even) / 1 (odd) takes with kernel index k: even rows take k = 1 from row m; odd rows
 // take k = 0 from row m + 1 and k = 2 from row m

@@ -1871,7 +1871,9 @@ CONV3X3S2_ENABLED = _os.environ.get("CABINET_CONV3X3S2", "1") != "0"
 def conv3x3s2_supported(conv, x):
     """True for the bias-free 3x3 stride-2 padding-1 convolutions whose BACKWARD K15 computes straight on NCHW (the spatial
     branch's conv2 / conv3, reference cabinet.py:112-113, and the backbone's first layer, mobilenetv3.py:173) -- in a forward
-    that records a graph for autograd only; fp32 device tensors outside autocast.  The forward stays the stock operator's."""
+    that records a graph for autograd only; fp32 device tensors outside autocast.  The forward stays the stock operator's; which
+    gradient of which layer goes native is _Conv3x3S2's business (64 -> 64: dx always, dw by _conv3x3s2_native_wgrad64; 3 -> 16: dw
+    by _conv3x3s2_native_wgrad)."""
     if not (CONV3X3S2_ENABLED and isinstance(conv, torch.nn.Conv2d) and x.is_cuda and x.dim() == 4):
         return False
     if not (conv.kernel_size == (3, 3) and conv.stride == (2, 2) and conv.padding == (1, 1) and conv.groups == 1
@@ -1885,17 +1887,44 @@ def conv3x3s2_supported(conv, x):
 
 
 def _conv3x3s2_native_wgrad(Ci, B, H):
-    """Where cabinet_conv3x3s2_wgrad is routed, by measurement on MI355X (tools/time_conv3x3s2.py, profiles/conv3x3s2_summary.md):
-    the 3 -> 16 form where its one workgroup per four output rows fills the chip (>= 1024 of them: x1.5 at config 3; with the 512
-    of config 5 it only draws level with the stock call).  The 64 -> 64 form is 0.5-0.6x the stock call, layout copies included, and
-    is not routed."""
+    """The routing rule of the 3 -> 16 form of cabinet_conv3x3s2_wgrad, by measurement on MI355X (tools/time_conv3x3s2.py,
+    profiles/conv3x3s2_summary.md): native where its one workgroup per four output rows fills the chip (>= 1024 of them: x1.5 at
+    config 3; with the 512 of config 5 it only draws level with the stock call).  False for every other channel count: the
+    64 -> 64 form has a rule of its own, _conv3x3s2_native_wgrad64."""
     return Ci == 3 and B * (((H - 1) // 2 + 1 + 3) // 4) >= 1024
+
+
+# CABINET_CONV3X3S2_WGRAD64=0: the 64 -> 64 weight gradient alone goes back to the stock operator -- same-box A/B timing only
+CONV3X3S2_WGRAD64_ENABLED = _os.environ.get("CABINET_CONV3X3S2_WGRAD64", "1") != "0"
+_CW_MIN_WORKGROUPS = 256  # one per CU
+_CW_MIN_ROWS = 4          # output rows a workgroup walks per 147 KB slab it writes: a full strip of cw_plan
+
+
+def _conv3x3s2_wgrad64_plan(B, H, W):
+    """cw_plan of csrc/conv3x3_s2.hip restated -> (workgroups, rows_per): 32-column tiles, strips of output rows."""
+    Ho, Wo = (H - 1) // 2 + 1, (W - 1) // 2 + 1
+    tiles = -(-Wo // 32)
+    strips = max(1, min(512 // (B * tiles), -(-Ho // 4)))
+    rows_per = -(-Ho // strips)
+    return B * tiles * -(-Ho // rows_per), rows_per
+
+
+def _conv3x3s2_native_wgrad64(B, H, W):
+    """The routing rule of the 64 -> 64 form of cabinet_conv3x3s2_wgrad, by measurement on MI355X
+    (tools/time_conv3x3s2_wgrad64.py, profiles/conv3x3s2_wgrad64_summary.md): native where the plan gives every CU a workgroup
+    and every workgroup a full strip of rows to pipeline over, which is where it was measured against the stock call with its
+    layout copies (sb.conv2 and sb.conv3 at config 3 and 5: 512 workgroups of 32, 8, 16 and 4 rows).  Smaller planes were not
+    measured and keep the stock operator."""
+    if not CONV3X3S2_WGRAD64_ENABLED:
+        return False
+    workgroups, rows_per = _conv3x3s2_wgrad64_plan(B, H, W)
+    return workgroups >= _CW_MIN_WORKGROUPS and rows_per >= _CW_MIN_ROWS
 
 
 class _Conv3x3S2(torch.autograd.Function):
     """y = conv2d(x, weight, stride 2, padding 1) with the stock forward; dx of the 64 -> 64 layers by cabinet_conv3x3s2_dgrad
-    (the 3 -> 16 layer reads the image and has none), dw by cabinet_conv3x3s2_wgrad where _conv3x3s2_native_wgrad says so,
-    else by the stock operator."""
+    (the 3 -> 16 layer reads the image and has none), dw by cabinet_conv3x3s2_wgrad where the form's rule says so
+    (_conv3x3s2_native_wgrad64 for 64 -> 64, _conv3x3s2_native_wgrad for 3 -> 16), else by the stock operator."""
 
     @staticmethod
     def forward(fn_ctx, x, weight):
@@ -1922,7 +1951,8 @@ class _Conv3x3S2(torch.autograd.Function):
         elif fn_ctx.needs_input_grad[0]:
             dx = cb(g, x, w, None, [2, 2], [1, 1], [1, 1], False, [0, 0], 1, [True, False, False])[0]
         dw = None
-        if fn_ctx.needs_input_grad[1] and _conv3x3s2_native_wgrad(Ci, B, H):
+        native_dw = _conv3x3s2_native_wgrad64(B, H, W) if Ci == 64 else _conv3x3s2_native_wgrad(Ci, B, H)
+        if fn_ctx.needs_input_grad[1] and native_dw:
             dw = torch.empty((Co, Ci, 3, 3), dtype=torch.float32, device=x.device)
             ws, nbytes = _workspace(lib.cabinet_conv3x3s2_wgrad_workspace_bytes(B, Ci, Co, H, W), x.device)
             with torch.cuda.device(x.device):
