@@ -23,7 +23,8 @@ ONE dispatch rule for every operator here:
   * device tensor, shape outside the coverage (attention channel pairs other than (128,128) (256,128) (64,64); producers
     with channel counts that are not multiples of 16; depthwise kernels other than 3 / 5; the local branch only for planes
     wider than its LDS tile, > ~1800 columns -- every B*H*W is served: channel-resident kernel up to 8192 positions per
-    channel, tiled multi-workgroup form above): the module's composite ATen forward, on the device -- the reference API accepts any
+    channel, tiled multi-workgroup form above; the loss heads beyond 32 classes, a 60 KB row of C * Wl logits or a resize ratio
+    whose segment buffers leave the LDS): the module's composite ATen forward, on the device -- the reference API accepts any
     channel count, so must this one;
   * host (CPU) tensors: the composite ATen forward, so modules stay usable for checkpoint surgery, EMA copies and CPU
     unit tests, exactly like any nn.Module.
@@ -490,6 +491,18 @@ def _class_weight(weight, logits, criterion="OhemCELoss"):
     if weight.dim() != 1 or weight.shape[0] != logits.shape[1]:
         raise RuntimeError(f"{criterion}: weight of shape {tuple(weight.shape)} for {logits.shape[1]} classes")
     return _f32c(weight.detach().to(logits.device))
+
+
+def ohem_up_supported(logits_low, size):
+    """The fused OHEM head takes these logits: HIP, (B,C,Hl,Wl) with C <= 32, a row of C * Wl floats and the segment buffers
+    of the resize ratio inside the kernels' LDS, B and H inside the grid.  The library's own rule (``check_ohem``: the focal
+    query with gamma = 0 is exactly that check for one image), asked before anything is launched."""
+    if not logits_low.is_cuda or logits_low.dim() != 4 or len(size) != 2:
+        return False
+    B, C, Hl, Wl = logits_low.shape
+    if B > 65535:  # the query is per image; check_ohem also bounds the batch (grid.y)
+        return False
+    return bool(_lib.load().cabinet_focal_up_supported(C, Hl, Wl, int(size[0]), int(size[1]), 0.0))
 
 
 def ohem_up_fwd_hip(logits_low, labels, size, thresh, ignore_lb, weight=None):

@@ -21,6 +21,16 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 
+def _ohem_fused(logits_low, size):
+    """The fused OHEM head takes this call: HIP logits of a shape the library accepts (asked before anything is launched, so a
+    shape outside the kernels' coverage takes the composite path instead of raising from the launch)."""
+    if not (logits_low.is_cuda and logits_low.dim() == 4 and logits_low.shape[1] <= 32):
+        return False
+    from .functional import ohem_up_supported
+
+    return ohem_up_supported(logits_low, size)
+
+
 class OhemCELoss(nn.Module):
     def __init__(self, thresh, n_min, ignore_lb=255, weight=None, device_select=False):
         super().__init__()
@@ -54,8 +64,10 @@ class OhemCELoss(nn.Module):
         into hand-written kernels on HIP tensors (``cabinet_ohem_up_fwd/bwd``): neither the (B,C,H,W) logits nor
         their log-softmax nor the per-pixel gradient are materialised.  The kernels implement the branch
         "at least n_min pixels above thresh", with or without class weights (non-negative, as the reference's ENet
-        weights are; the weight buffer is read by the kernels, it gets no gradient); CPU tensors and more than 32 classes
-        take the composite path, and so does the top-n_min branch unless the criterion was built with
+        weights are; the weight buffer is read by the kernels, it gets no gradient).  CPU tensors and every shape the library
+        refuses (``functional.ohem_up_supported``: more than 32 classes; a row of C * Wl floats above 60 KB, e.g. 19 classes at
+        Wl = 809; a resize ratio whose segment buffers do not fit, e.g. Wl = 1 -> W = 300; B or H above 65535) take the
+        composite path, on the tensors' device, and so does the top-n_min branch unless the criterion was built with
         ``device_select=True``: then that branch runs on the kernels too (k-th largest loss by a radix select on the device,
         backward with a device threshold; a k-th value that is tied spreads its weight evenly over the tied pixels)."""
         prep = self._fused_launch(logits_low, labels, size)
@@ -65,8 +77,7 @@ class OhemCELoss(nn.Module):
     # and pay ONE host read-back for the branch decisions (see ohem_upsampled_pair).
     def _fused_launch(self, logits_low, labels, size):
         size = tuple(size) if size is not None else tuple(labels.shape[-2:])
-        fused = logits_low.is_cuda and logits_low.shape[1] <= 32
-        if not fused:
+        if not _ohem_fused(logits_low, size):
             return (logits_low, labels, size, None, None, None)
         from .functional import _f32c, ohem_up_fwd_hip
 
@@ -223,8 +234,8 @@ def fused_pair_launch(crit_a, low_a, crit_b, low_b, labels, size):
     else one launch per head.  Each head brings its own class weights or none: the two criteria own separate buffers, and the
     kernels take one table per head.  No host synchronisation: ``prep.stats`` is a device tensor."""
     size = tuple(size) if size is not None else tuple(labels.shape[-2:])
-    same = (low_a.is_cuda and low_b.is_cuda and low_a.shape == low_b.shape and low_a.shape[1] <= 32
-            and (crit_a.thresh, crit_a.ignore_lb) == (crit_b.thresh, crit_b.ignore_lb))
+    same = (low_a.is_cuda and low_b.is_cuda and low_a.shape == low_b.shape
+            and (crit_a.thresh, crit_a.ignore_lb) == (crit_b.thresh, crit_b.ignore_lb) and _ohem_fused(low_a, size))
     if not same:
         return _PairPrep((crit_a, crit_b), (low_a, low_b), labels, size,
                          heads=(crit_a._fused_launch(low_a, labels, size), crit_b._fused_launch(low_b, labels, size)))

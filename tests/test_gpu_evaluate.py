@@ -101,12 +101,26 @@ def test_scale_merge_vs_float64(C, src, crop, out):
         assert err < 5e-7
 
 
-@pytest.mark.parametrize("C,H,W", [(1, 16, 24), (8, 96, 200), (19, 61, 131), (32, 64, 64)])
+def _argmax_hist_plan(N, H, W):
+    """eval_argmax_hist_run (eval_tail.hip:290-311) -> (VEC, groups, workgroups): VEC pixels per thread, at most 512 workgroups of
+    256 threads that stride over the groups."""
+    vec = 4 if (H * W) % 4 == 0 else 1
+    groups = N * (H * W // vec)
+    return vec, groups, min(-(-groups // 256), 512)
+
+
+# the last two cross the cap of 512 workgroups (more than 512 * 256 groups): the second trip of the kernel's strided loop, with
+# VEC = 4 and -- P odd -- with VEC = 1
+@pytest.mark.parametrize("C,H,W", [(1, 16, 24), (8, 96, 200), (19, 61, 131), (32, 64, 64), (8, 728, 728), (19, 363, 363)])
 def test_argmax_hist_ties_clip_ignore(C, H, W):
     from cabinet_amd.functional import eval_argmax_hist
 
     g = torch.Generator().manual_seed(C + W)
     N = 2
+    if H >= 363:
+        vec, groups, wgs = _argmax_hist_plan(N, H, W)
+        assert vec == (4 if H == 728 else 1) and groups > 512 * 256 and wgs == 512
+        assert _argmax_hist_plan(1, H, W)[1] == (132496 if H == 728 else 131769) > 512 * 256   # one image alone crosses it
     total = torch.rand(N, C, H, W, generator=g)
     if C >= 8:  # exact ties: the same maximal value in two (three) classes, the lowest index must win
         tie = torch.rand(N, H, W, generator=g) < 0.2

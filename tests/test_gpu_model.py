@@ -473,6 +473,16 @@ def test_one_dispatch_rule_for_shapes_outside_kernel_coverage():
     out = cab_attention(q, q.detach(), q.detach(), 0.2)  # composite on the device
     out.sum().backward()
     assert out.is_cuda and q.grad is not None
+    # the fused OHEM head follows the same rule: one source column resized to 300 needs segment buffers beyond the LDS
+    from cabinet_amd.functional import ohem_up_supported
+    from cabinet_amd.loss import OhemCELoss
+
+    low = torch.randn(1, 8, 1, 1, device="cuda", requires_grad=True)
+    lab = torch.randint(0, 8, (1, 1, 300), device="cuda")
+    assert ohem_up_supported(low, (1, 8)) and not ohem_up_supported(low, (1, 300))
+    loss = OhemCELoss(0.7, 16, 255).forward_upsampled(low, lab, (1, 300))  # composite on the device
+    loss.backward()
+    assert loss.is_cuda and "_OhemUp" not in type(loss.grad_fn).__name__ and low.grad is not None
 
     def run(C, Vc, B, H, W, seed):
         torch.manual_seed(seed)
