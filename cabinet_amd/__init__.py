@@ -8,7 +8,7 @@
 * ``cabinet_amd.train``      the reference's train step (train.py:429-441) as a harness
 * ``cabinet_amd.evaluate``   the reference's multi-scale evaluator (mIoU) with its probability tail in HIP kernels
 * ``cabinet_amd.predict``    the reference's single-image inference and visualisation with the label / render tail in HIP kernels
-* ``cabinet_amd.augment``    the reference's Cityscapes train transform for batches on the device (two HIP launches)
+* ``cabinet_amd.augment``    the reference's Cityscapes and aerial (UAVid, VDD, AeroScapes) train transforms for batches on the device
 """
 import os as _os
 

@@ -138,6 +138,9 @@ SIGNATURES = {
     "cabinet_augment_supported": (_INT, [_INT] * 7),
     "cabinet_augment_workspace_bytes": (_SZ, [_INT] * 3),
     "cabinet_augment_batch": (_INT, [_PTR] + [_INT] * 3 + [_PTR, ctypes.c_ulonglong] + [_PTR] * 5 + [_PTR, _SZ, _PTR]),
+    "cabinet_augment_warp_supported": (_INT, [_INT] * 4 + [ctypes.c_double] * 2),
+    "cabinet_augment_warp_batch": (_INT, [_PTR] + [_INT] * 3 + [_PTR]),
+    "cabinet_augment_resize_batch": (_INT, [_PTR] + [_INT] * 3 + [_PTR]),
 }
 
 _lock = threading.Lock()

@@ -16,6 +16,17 @@ taps of Pillow's antialiased resample with their 22-bit integer coefficients, an
 and the reflection (a padded column takes the taps of its mirror column) are applied per sample.  The kernels then only walk
 tables and do per-pixel integer and fp32 arithmetic.
 
+The aerial datasets (src/datasets/uavid.py:192-230, vdd.py, aeroscapes.py; K20, csrc/augment_warp.hip) put ResizeIfLarger, a
+vertical flip, RandomTranslate and RandomRotate(expand=True) ahead of the scale and RandomHSV behind the crop:
+
+    aug = DeviceAugment.uavid(cropsize=(1024, 1024))     # or .vdd / .aeroscapes / .aerial(cropsize, augmentation={...})
+    im, lb = aug(images, labels, rng=random.Random(seed))
+    im, lb = DeviceAugment.mixup(im_a, lb_a, im_b, lb_b, r)
+
+Those steps run as uint8 -> uint8 passes (Pillow truncates to bytes between them): resize where the source is larger than the
+cap, translate with both flips folded into its source read, rotate; their output is the `image` / `label` of the two launches
+above, whose geometry kernel also applies the HSV tables.
+
 Routing: device tensors take the kernels and never fall back (a shape the kernels refuse raises); host tensors take the numpy
 path below, which uses the same tables and the same arithmetic.
 """
@@ -23,6 +34,8 @@ path below, which uses the same tables and the same arithmetic.
 from __future__ import annotations
 
 import ctypes as _ct
+import functools as _functools
+import math as _math
 import random as _random
 from dataclasses import dataclass
 from typing import List, Optional, Sequence, Tuple
@@ -32,14 +45,19 @@ import torch
 
 from . import _lib
 
-__all__ = ["DeviceAugment", "SampleParams", "resample_taps", "nearest_index", "MAX_TAPS"]
+__all__ = ["DeviceAugment", "SampleParams", "resample_taps", "nearest_index", "MAX_TAPS", "resize_if_larger", "rotate_matrix",
+           "affine_image", "affine_label", "rgb_to_hsv", "hsv_to_rgb", "hsv_tables", "warp_descs"]
 
 MAX_TAPS = 5
 MAX_RATIO = 2.5                  # resize ratio in/out per axis: five taps at most, and fewer than 17 * 2.5 + 1 source rows per tile
 TILE_ROWS, TILE_SPAN = 16, 48    # csrc/augment.hip: output rows of a workgroup tile, source rows it stages
 _TABLE_CACHE = 32                # axis tables kept (Cityscapes' six scales need twelve); continuous scales evict the oldest
 _PRECISION_BITS = 22
-FLAG_GRAY, FLAG_GAMMA, FLAG_NOISE, FLAG_CUTOUT = 1, 2, 4, 8
+FLAG_GRAY, FLAG_GAMMA, FLAG_NOISE, FLAG_CUTOUT, FLAG_HSV = 1, 2, 4, 8, 16
+MAX_ANGLE = 45.0                 # csrc/augment_warp.hip: the rotation pass covers 0 < |angle| <= 45 degrees (and 0, a copy)
+MAX_SIDE = 32768
+LABEL_TABLES, LABEL_FIXED = 0, 1
+FLIP_X, FLIP_Y = 1, 2
 
 # One table entry per sample; mirrors `cabinet_augment_sample` in include/cabinet_hip.h (2400 bytes)
 SAMPLE_DTYPE = np.dtype([
@@ -51,7 +69,14 @@ SAMPLE_DTYPE = np.dtype([
     ("gamma_lut", "u1", (256,)), ("label_lut", "<i8", (256,)),
 ])
 TAP_DTYPE = np.dtype([("first", "<i4"), ("step", "<i4"), ("n", "<i4"), ("coef", "<i4", (MAX_TAPS,))])  # 32 bytes
-assert SAMPLE_DTYPE.itemsize == 2400 and TAP_DTYPE.itemsize == 32
+# One descriptor per sample and pass; mirrors `cabinet_augment_warp_desc` in include/cabinet_hip.h (192 bytes)
+WARP_DTYPE = np.dtype([
+    ("src_image", "<u8"), ("src_label", "<u8"), ("dst_image", "<u8"), ("dst_label", "<u8"),
+    ("H", "<i4"), ("W", "<i4"), ("out_h", "<i4"), ("out_w", "<i4"), ("a", "<f8", (6,)), ("fix", "<i8", (6,)),
+    ("lab_col", "<u8"), ("lab_row", "<u8"), ("col_taps", "<u8"), ("row_taps", "<u8"),
+    ("flip", "<i4"), ("label_mode", "<i4"), ("fill", "<i4"), ("reserved", "<i4"),
+])
+assert SAMPLE_DTYPE.itemsize == 2400 and TAP_DTYPE.itemsize == 32 and WARP_DTYPE.itemsize == 192
 
 
 # --------------------------------------------------------------------------- tables
@@ -107,6 +132,202 @@ class _AxisTables(object):
         self.label = nearest_index(n_in, n_out)
 
 
+@_functools.lru_cache(maxsize=8)
+def _resize_axis(n_in: int, n_out: int):
+    """(taps, label index) of a whole resized axis, unflipped: ResizeIfLarger meets a handful of sizes per dataset."""
+    tab = _AxisTables(n_in, n_out)
+    taps = np.zeros(n_out, dtype=TAP_DTYPE)
+    taps["first"], taps["step"], taps["n"], taps["coef"] = tab.first, 1, tab.n, tab.coef
+    return taps, tab.label
+
+
+# --------------------------------------------------------------------------- aerial geometry (K20): Pillow's arithmetic, restated
+
+def resize_if_larger(H: int, W: int, cap) -> Optional[Tuple[int, int]]:
+    """ResizeIfLarger's target (h, w), or None where it does not act."""
+    if cap is None or max(W, H) <= cap:
+        return None
+    scale = cap / max(W, H)
+    return max(1, round(H * scale)), max(1, round(W * scale))
+
+
+def rotate_matrix(W: int, H: int, angle: float):
+    """Image.rotate(angle, expand=True): (the six coefficients, nw, nh), or None for an angle that is a copy."""
+    angle = angle % 360.0
+    if angle == 0:
+        return None
+    r = -_math.radians(angle)
+    m = [round(_math.cos(r), 15), round(_math.sin(r), 15), 0.0, round(-_math.sin(r), 15), round(_math.cos(r), 15), 0.0]
+
+    def T(x, y):
+        return m[0] * x + m[1] * y + m[2], m[3] * x + m[4] * y + m[5]
+
+    m[2], m[5] = T(-(W / 2.0), -(H / 2.0))
+    m[2] += W / 2.0
+    m[5] += H / 2.0
+    xs, ys = zip(*[T(x, y) for x, y in ((0, 0), (W, 0), (W, H), (0, H))])
+    nw = _math.ceil(max(xs)) - _math.floor(min(xs))
+    nh = _math.ceil(max(ys)) - _math.floor(min(ys))
+    m[2], m[5] = T(-(nw - W) / 2.0, -(nh - H) / 2.0)
+    return tuple(m), int(nw), int(nh)
+
+
+def _flipped(src, flip):
+    src = src[:, ::-1] if flip & FLIP_X else src
+    return src[::-1] if flip & FLIP_Y else src
+
+
+def affine_image(src: np.ndarray, a, out_w: int, out_h: int, flip: int = 0) -> np.ndarray:
+    """Image.transform((out_w, out_h), AFFINE, a, BILINEAR) of uint8 (H, W, 3), read through ``flip``: double, every operation
+    rounded on its own, the byte by truncation; outside the source 0."""
+    src = _flipped(src, flip)
+    H, W = src.shape[:2]
+    a = [float(v) for v in a]
+    out = np.zeros((out_h, out_w, 3), dtype=np.uint8)
+    xh = np.arange(out_w, dtype=np.float64) + 0.5
+    ax0, ax3 = a[0] * xh, a[3] * xh
+    for y0 in range(0, out_h, 128):
+        yh = np.arange(y0, min(out_h, y0 + 128), dtype=np.float64) + 0.5
+        xin = (ax0[None, :] + (a[1] * yh)[:, None]) + a[2]
+        yin = (ax3[None, :] + (a[4] * yh)[:, None]) + a[5]
+        ok = (xin >= 0) & (xin < W) & (yin >= 0) & (yin < H)
+        if not ok.any():
+            continue
+        xs, ys = np.where(ok, xin, 0.5) - 0.5, np.where(ok, yin, 0.5) - 0.5
+        xf, yf = np.floor(xs), np.floor(ys)
+        dx, dy = (xs - xf)[..., None], (ys - yf)[..., None]
+        xf, yf = xf.astype(np.int64), yf.astype(np.int64)
+        c0, c1 = np.clip(xf, 0, W - 1), np.clip(xf + 1, 0, W - 1)
+        r0, r1 = np.clip(yf, 0, H - 1), np.clip(yf + 1, 0, H - 1)
+        below = ((yf + 1 >= 0) & (yf + 1 < H))[..., None]
+        p00, p01 = src[r0, c0].astype(np.float64), src[r0, c1].astype(np.float64)
+        p10, p11 = src[r1, c0].astype(np.float64), src[r1, c1].astype(np.float64)
+        v1 = p00 + (p01 - p00) * dx
+        v2 = np.where(below, p10 + (p11 - p10) * dx, v1)
+        v = v1 + (v2 - v1) * dy
+        out[y0:y0 + yh.size] = np.where(ok[..., None], v.astype(np.uint8), 0)
+    return out
+
+
+def _fix16(v: float) -> int:
+    return int(_math.floor(v * 65536.0 + 0.5))
+
+
+def affine_fixed(a) -> Tuple[int, ...]:
+    """Pillow's 16.16 coefficients of a general affine NEAREST transform."""
+    a = [float(v) for v in a]
+    return (_fix16(a[0]), _fix16(a[1]), _fix16(a[2] + a[0] * 0.5 + a[1] * 0.5),
+            _fix16(a[3]), _fix16(a[4]), _fix16(a[5] + a[3] * 0.5 + a[4] * 0.5))
+
+
+def affine_axis_table(offset: float, step: float, n_out: int, n_in: int) -> np.ndarray:
+    """Pillow's per-axis table of an axis-aligned NEAREST transform: xo from offset + step / 2 by a running sum in double; the
+    entry is (int) xo, -1 where xo < 0 or the index is past the source."""
+    steps = np.full(n_out, float(step), dtype=np.float64)
+    steps[0] = float(offset) + float(step) * 0.5
+    xo = np.cumsum(steps)   # a running sum in index order
+    idx = np.where(xo < 0, -1.0, np.trunc(np.clip(xo, -1.0, float(n_in)))).astype(np.int64)
+    return np.where(idx >= n_in, -1, idx).astype(np.int32)
+
+
+def affine_label(src: np.ndarray, a, out_w: int, out_h: int, fill: int, flip: int = 0) -> np.ndarray:
+    """Image.transform((out_w, out_h), AFFINE, a, NEAREST, fillcolor=fill) of uint8 (H, W), read through ``flip``: per-axis
+    tables where a[1] == a[3] == 0, Pillow's 16.16 fixed point otherwise."""
+    src = _flipped(src, flip)
+    H, W = src.shape
+    a = [float(v) for v in a]
+    if a[1] == 0 and a[3] == 0:
+        lc, lr = affine_axis_table(a[2], a[0], out_w, W)[None, :], affine_axis_table(a[5], a[4], out_h, H)[:, None]
+    else:
+        A = affine_fixed(a)
+        x, y = np.arange(out_w, dtype=np.int64)[None, :], np.arange(out_h, dtype=np.int64)[:, None]
+        lc, lr = (A[2] + y * A[1] + x * A[0]) >> 16, (A[5] + y * A[4] + x * A[3]) >> 16
+    ok = (lc >= 0) & (lc < W) & (lr >= 0) & (lr < H)
+    return np.where(ok, src[np.clip(lr, 0, H - 1), np.clip(lc, 0, W - 1)], fill).astype(np.uint8)
+
+
+def rgb_to_hsv(a: np.ndarray) -> np.ndarray:
+    """Pillow's convert("HSV") of uint8 (..., 3): fp32 divisions, the hue's sum and wrap in double."""
+    r, g, b = [a[..., i].astype(np.int32) for i in range(3)]
+    mx, mn = np.maximum(r, np.maximum(g, b)), np.minimum(r, np.minimum(g, b))
+    ok = mx != mn
+    cr = np.where(ok, mx - mn, 1).astype(np.float32)
+    s = cr / np.where(ok, mx, 1).astype(np.float32)
+    rc, gc, bc = [(mx - c).astype(np.float32) / cr for c in (r, g, b)]
+    rc64, gc64, bc64 = rc.astype(np.float64), gc.astype(np.float64), bc.astype(np.float64)
+    h = np.where(r == mx, bc - gc, np.where(g == mx, ((2.0 + rc64) - bc64).astype(np.float32), ((4.0 + gc64) - rc64).astype(np.float32)))
+    h = np.fmod(h.astype(np.float32).astype(np.float64) / 6.0 + 1.0, 1.0).astype(np.float32)
+    H = np.clip((h.astype(np.float64) * 255.0).astype(np.int64), 0, 255)
+    S = np.clip((s.astype(np.float64) * 255.0).astype(np.int64), 0, 255)
+    return np.stack([np.where(ok, H, 0), np.where(ok, S, 0), mx], axis=-1).astype(np.uint8)
+
+
+def hsv_to_rgb(a: np.ndarray) -> np.ndarray:
+    """Pillow's HSV -> RGB of uint8 (..., 3): f and S / 255 rounded to fp32, the products in double, C's round."""
+    H, S, V = [a[..., i].astype(np.float64) for i in range(3)]
+    hh = H * 6.0 / 255.0
+    i = np.floor(hh)
+    f = (hh - i).astype(np.float32).astype(np.float64)
+    fs = (S / 255.0).astype(np.float32).astype(np.float64)
+    cround = lambda v: np.clip(np.floor(v + 0.5), 0, 255)  # noqa: E731  (C's round of a non-negative value)
+    p, q, t = cround(V * (1.0 - fs)), cround(V * (1.0 - fs * f)), cround(V * (1.0 - fs * (1.0 - f)))
+    k = i.astype(np.int64) % 6
+    R, G, B = np.choose(k, [V, q, p, p, t, V]), np.choose(k, [t, V, V, q, p, p]), np.choose(k, [p, p, t, V, V, q])
+    out = np.stack([R, G, B], axis=-1)
+    return np.where((a[..., 1] == 0)[..., None], V[..., None], out).astype(np.uint8)
+
+
+def hsv_tables(r_h: float, r_s: float, r_v: float) -> np.ndarray:
+    """RandomHSV's three byte tables (3, 256), by the reference's numpy expressions on every byte value."""
+    hsv = np.repeat(np.arange(256, dtype=np.int16)[:, None], 3, axis=1)
+    hsv[..., 0] = (hsv[..., 0] + round(r_h * 255)) % 255
+    hsv[..., 1] = np.clip(hsv[..., 1] * (r_s + 1), 0, 255)
+    hsv[..., 2] = np.clip(hsv[..., 2] * (r_v + 1), 0, 255)
+    return np.ascontiguousarray(hsv.astype(np.uint8).T)
+
+
+def apply_hsv(im: np.ndarray, tables: np.ndarray) -> np.ndarray:
+    hsv = rgb_to_hsv(im)
+    return hsv_to_rgb(np.stack([tables[0][hsv[..., 0]], tables[1][hsv[..., 1]], tables[2][hsv[..., 2]]], axis=-1))
+
+
+def warp_descs(items) -> np.ndarray:
+    """The device block of cabinet_augment_warp_batch / cabinet_augment_resize_batch as host bytes: one cabinet_augment_warp_desc
+    per item, then the tables they name.  An item is a dict with src_image, src_label, dst_image, dst_label (device addresses),
+    H, W, out_h, out_w and either ``a`` (six coefficients; optional ``flip`` and ``fill``) for the affine pass -- the label
+    route follows Pillow's choice -- or ``resize=True`` for the resize pass."""
+    a16 = lambda v: (v + 15) & ~15  # noqa: E731
+    head = a16(len(items) * WARP_DTYPE.itemsize)
+    tables, off = [], head
+    entries = np.zeros(len(items), dtype=WARP_DTYPE)
+    for e, it in zip(entries, items):
+        for k in ("src_image", "src_label", "dst_image", "dst_label", "H", "W", "out_h", "out_w"):
+            e[k] = it[k]
+        H, W, oh, ow = int(it["H"]), int(it["W"]), int(it["out_h"]), int(it["out_w"])
+        named = []
+        if it.get("resize"):
+            (ct, lc), (rt, lr) = _resize_axis(W, ow), _resize_axis(H, oh)
+            named += [("col_taps", ct), ("row_taps", rt), ("lab_col", lc), ("lab_row", lr)]
+        else:
+            a = [float(v) for v in it["a"]]
+            e["a"], e["flip"], e["fill"] = a, int(it.get("flip", 0)), int(it.get("fill", 0))
+            if a[1] == 0 and a[3] == 0:
+                e["label_mode"] = LABEL_TABLES
+                named += [("lab_col", affine_axis_table(a[2], a[0], ow, W)), ("lab_row", affine_axis_table(a[5], a[4], oh, H))]
+            else:
+                e["label_mode"], e["fix"] = LABEL_FIXED, affine_fixed(a)
+        for name, arr in named:
+            raw = np.ascontiguousarray(arr).view(np.uint8).reshape(-1)
+            e[name] = off
+            tables.append((off, raw))
+            off += a16(raw.size)
+    blob = np.zeros(off, dtype=np.uint8)
+    blob[:entries.nbytes] = entries.view(np.uint8)
+    for o, raw in tables:
+        blob[o:o + raw.size] = raw
+    return blob
+
+
 @dataclass
 class SampleParams:
     """What the reference's Compose draws for one sample, in its order."""
@@ -123,16 +344,30 @@ class SampleParams:
     gamma: Optional[float]
     noise: bool
     cutout: Optional[Tuple[int, int]]   # (y, x)
+    # the aerial steps (K20); the defaults are "the step is absent"
+    vflip: bool = False
+    dx: float = 0.0                               # RandomTranslate, in pixels of the (resized) source
+    dy: float = 0.0
+    angle: float = 0.0                            # RandomRotate, degrees
+    hsv: Optional[Tuple[float, float, float]] = None   # RandomHSV's r_h, r_s, r_v (gain times uniform(-1, 1))
+    resized: Optional[Tuple[int, int]] = None     # (H, W) after ResizeIfLarger, None where it does not act
+    warped: Optional[Tuple[int, int]] = None      # (H, W) entering RandomScale, None without the aerial geometry
 
 
 class DeviceAugment(object):
     """The reference's train-time transform for batches; see the module docstring.  ``cropsize`` is (target_w, target_h), the
     order of the reference's RandomCrop.  ``brightness`` / ``contrast`` / ``saturation`` are the reference's jitter widths
-    (``v`` -> uniform(max(1 - v, 0), 1 + v)) or None.  ``label_map``: 256 entries id -> trainId, or None for the identity."""
+    (``v`` -> uniform(max(1 - v, 0), 1 + v)) or None.  ``label_map``: 256 entries id -> trainId, or None for the identity.
+
+    The aerial datasets' steps, each absent at None: ``max_size`` (ResizeIfLarger's cap), ``vflip_p``, ``translate`` (fraction of
+    the size), ``degrees`` (RandomRotate over (-degrees, degrees), expand=True) -- any of these four runs the whole chain
+    resize, flips, translate, rotate ahead of the scale, as the reference's pipeline holds all of them -- and ``hsv`` =
+    (hgain, sgain, vgain) of RandomHSV behind the crop.  ``grayscale_p=None``: a pipeline without the grayscale step."""
 
     def __init__(self, cropsize, ignore_label=255, label_map=None, scales=(1.0,), continuous=False, flip_p=0.5, brightness=None,
                  contrast=None, saturation=None, grayscale_p=0.0, gamma_range=(0.7, 1.5), gamma_p=0.0, noise_sigma=0.05,
-                 noise_p=0.0, cutout_p=0.0, cutout_size=64, mean=(0.485, 0.456, 0.406), std=(0.229, 0.224, 0.225), seed=None):
+                 noise_p=0.0, cutout_p=0.0, cutout_size=64, mean=(0.485, 0.456, 0.406), std=(0.229, 0.224, 0.225), seed=None,
+                 max_size=None, vflip_p=None, translate=None, degrees=None, hsv=None):
         self.tw, self.th = int(cropsize[0]), int(cropsize[1])
         if self.tw < 1 or self.th < 1:
             raise ValueError(f"DeviceAugment: cropsize {cropsize} must be positive")
@@ -148,13 +383,27 @@ class DeviceAugment(object):
         self.flip_p = float(flip_p)
         jit = lambda v: None if v is None else (max(1 - v, 0), 1 + v)  # noqa: E731  (RandomColorJitter._check)
         self.brightness, self.contrast, self.saturation = jit(brightness), jit(contrast), jit(saturation)
-        self.grayscale_p, self.gamma_range, self.gamma_p = float(grayscale_p), tuple(gamma_range), float(gamma_p)
+        # grayscale_p=None: the pipeline has no RandomGrayscale step at all (the aerial datasets'), so nothing is drawn for it
+        self.grayscale_p = None if grayscale_p is None else float(grayscale_p)
+        self.gamma_range, self.gamma_p = tuple(gamma_range), float(gamma_p)
         self.noise_sigma, self.noise_p = float(noise_sigma), float(noise_p)
         self.cutout_p, self.cutout_size = float(cutout_p), int(cutout_size)
         self.mean, self.std = tuple(float(v) for v in mean), tuple(float(v) for v in std)
         self._seed = _random.SystemRandom().getrandbits(63) if seed is None else int(seed)
         self._calls = 0
         self._tables = {}
+        # the aerial steps: any of the four geometric keywords puts the whole chain ResizeIfLarger, flips, RandomTranslate,
+        # RandomRotate ahead of RandomScale, each with "never" / zero width where its own keyword is None, drawn as the reference draws
+        self.aerial = any(v is not None for v in (max_size, vflip_p, translate, degrees))
+        self.max_size = None if max_size is None else int(max_size)
+        self.vflip_p = 0.0 if vflip_p is None else float(vflip_p)
+        self.translate = 0.0 if translate is None else float(translate)
+        self.degrees = 0.0 if degrees is None else float(degrees)
+        self.hsv = None if hsv is None else tuple(float(v) for v in hsv)
+        if self.hsv is not None and len(self.hsv) != 3:
+            raise ValueError("DeviceAugment: hsv takes (hgain, sgain, vgain)")
+        self.mixup_p = 0.0
+        self._buffers = {}
 
     @classmethod
     def cityscapes(cls, cropsize=(1024, 1024), ignore_label=255, label_map=None, **overrides):
@@ -163,6 +412,54 @@ class DeviceAugment(object):
                   grayscale_p=0.2, gamma_range=(0.8, 1.2), gamma_p=0.3, noise_sigma=0.03, noise_p=0.3, cutout_p=0.3, cutout_size=64)
         kw.update(overrides)
         return cls(cropsize, ignore_label=ignore_label, label_map=label_map, **kw)
+
+    AERIAL_DEFAULTS = dict(degrees=10.0, translate=0.05, scale=0.3, flipud=0.2, fliplr=0.5, hsv_h=0.01, hsv_s=0.4, hsv_v=0.3, mixup=0.1)
+
+    @classmethod
+    def aerial(cls, cropsize=(1024, 1024), augmentation=None, ignore_label=255, label_map=None, **overrides):
+        """The train pipeline the reference's aerial datasets share (src/datasets/uavid.py:192-230); ``augmentation`` takes the
+        reference's ``augmentation:`` keys over its defaults.  Its ``mixup`` probability is kept as ``mixup_p`` for the caller."""
+        unknown = set(augmentation or {}) - set(cls.AERIAL_DEFAULTS)
+        if unknown:
+            raise ValueError(f"DeviceAugment.aerial: unknown augmentation keys {sorted(unknown)}")
+        a = {**cls.AERIAL_DEFAULTS, **(augmentation or {})}
+        scale = float(a["scale"])
+        kw = dict(max_size=2 * max(cropsize), flip_p=float(a["fliplr"]), vflip_p=float(a["flipud"]), translate=float(a["translate"]),
+                  degrees=float(a["degrees"]), scales=(1.0 - scale, 1.0 + scale), continuous=True,
+                  hsv=(float(a["hsv_h"]), float(a["hsv_s"]), float(a["hsv_v"])), contrast=0.5, grayscale_p=None,
+                  gamma_range=(0.8, 1.2), gamma_p=0.3, noise_sigma=0.03, noise_p=0.3, cutout_p=0.3, cutout_size=64)
+        kw.update(overrides)
+        aug = cls(cropsize, ignore_label=ignore_label, label_map=label_map, **kw)
+        aug.mixup_p = float(a["mixup"])
+        return aug
+
+    @classmethod
+    def uavid(cls, cropsize=(1024, 1024), augmentation=None, **overrides):
+        """src/datasets/uavid.py: its normalisation constants."""
+        kw = dict(mean=(0.480, 0.499, 0.457), std=(0.225, 0.208, 0.228))
+        kw.update(overrides)
+        return cls.aerial(cropsize, augmentation, **kw)
+
+    @classmethod
+    def vdd(cls, cropsize=(1024, 1024), augmentation=None, **overrides):
+        """src/datasets/vdd.py."""
+        kw = dict(mean=(0.486, 0.487, 0.441), std=(0.190, 0.178, 0.214))
+        kw.update(overrides)
+        return cls.aerial(cropsize, augmentation, **kw)
+
+    @classmethod
+    def aeroscapes(cls, cropsize=(640, 640), augmentation=None, **overrides):
+        """src/datasets/aeroscapes.py."""
+        kw = dict(mean=(0.439, 0.508, 0.460), std=(0.176, 0.157, 0.194))
+        kw.update(overrides)
+        return cls.aerial(cropsize, augmentation, **kw)
+
+    @staticmethod
+    def mixup(im_a, lb_a, im_b, lb_b, r):
+        """The reference's MixUp (src/datasets/uavid.py:256-269) of two normalised fp32 tensors: im_a r + im_b (1 - r), each
+        product and the sum an operation of its own, and the whole label of whichever sample holds the larger share."""
+        r = float(r)
+        return im_a * r + im_b * (1.0 - r), (lb_a if r >= 0.5 else lb_b)
 
     # ------------------------------------------------------------------ parameters
 
@@ -173,15 +470,29 @@ class DeviceAugment(object):
         out = []
         for H, W in sizes:
             flip = not (rng.random() > self.flip_p)
+            extra = {}
+            if self.aerial:
+                resized = resize_if_larger(H, W, self.max_size)
+                H, W = resized if resized is not None else (H, W)
+                vflip = not (rng.random() > self.vflip_p)
+                dx = rng.uniform(-self.translate, self.translate) * W
+                dy = rng.uniform(-self.translate, self.translate) * H
+                angle = rng.uniform(-self.degrees, self.degrees)
+                rot = rotate_matrix(W, H, angle)
+                if rot is not None:
+                    H, W = rot[2], rot[1]
+                extra = dict(vflip=vflip, dx=dx, dy=dy, angle=angle, resized=resized, warped=(H, W))
             scale = rng.uniform(*self.scales) if self.continuous else rng.choice(self.scales)
             w, h = int(round(W * scale)), int(round(H * scale))
             pw, ph = max(w, self.tw), max(h, self.th)
             sw = rng.randint(0, pw - self.tw) if pw > self.tw else 0
             sh = rng.randint(0, ph - self.th) if ph > self.th else 0
+            if self.hsv is not None and any(self.hsv):
+                extra["hsv"] = tuple(rng.uniform(-1, 1) * g for g in self.hsv)
             rb = rng.uniform(*self.brightness) if self.brightness else 1.0
             rc = rng.uniform(*self.contrast) if self.contrast else 1.0
             rs = rng.uniform(*self.saturation) if self.saturation else 1.0
-            gray = rng.random() < self.grayscale_p
+            gray = False if self.grayscale_p is None else rng.random() < self.grayscale_p
             gamma = rng.uniform(*self.gamma_range) if rng.random() < self.gamma_p else None
             noise = rng.random() < self.noise_p
             cutout = None
@@ -189,7 +500,7 @@ class DeviceAugment(object):
                 y = rng.randint(0, self.th - self.cutout_size)
                 x = rng.randint(0, self.tw - self.cutout_size)
                 cutout = (y, x)
-            out.append(SampleParams(flip, scale, w, h, sw, sh, rb, rc, rs, gray, gamma, noise, cutout))
+            out.append(SampleParams(flip, scale, w, h, sw, sh, rb, rc, rs, gray, gamma, noise, cutout, **extra))
         return out
 
     def supported(self, size: Tuple[int, int], p: SampleParams) -> bool:
@@ -200,12 +511,57 @@ class DeviceAugment(object):
 
     def _limits(self, size, p: SampleParams):
         """(covered, taps, pad_y, pad_x) of one sample; the tap count is 0 where the ratio already rules the sample out."""
-        H, W = size
+        H, W = self._scale_source(size, p)
         pad_y, pad_x = max(self.th - p.h, 0), max(self.tw - p.w, 0)
+        if self._warp_refusal(size, p) is not None:
+            return False, 0, pad_y, pad_x
         if p.w < 1 or p.h < 1 or W > MAX_RATIO * p.w or H > MAX_RATIO * p.h:
             return False, 0, pad_y, pad_x
         taps = int(max(self._axis(W, p.w).n.max(), self._axis(H, p.h).n.max()))
         return bool(taps <= MAX_TAPS and pad_x <= p.w - 1 and pad_y <= p.h - 1), taps, pad_y, pad_x
+
+    def _scale_source(self, size, p: SampleParams):
+        """(H, W) of what RandomScale resizes: the source itself, or the output of the aerial geometry."""
+        if not self.aerial:
+            return size
+        if p.warped is None:
+            raise ValueError("DeviceAugment: the aerial steps need SampleParams from draw() (resized / warped sizes)")
+        return p.warped
+
+    def _warp_refusal(self, size, p: SampleParams) -> Optional[str]:
+        """The aerial step that refuses this sample, in words, or None."""
+        if not self.aerial:
+            return None
+        H, W = size
+        if max(H, W) > MAX_SIDE:
+            return f"the source side {max(H, W)} is above {MAX_SIDE}"
+        if p.resized is not None and (H > MAX_RATIO * p.resized[0] or W > MAX_RATIO * p.resized[1]):
+            return (f"ResizeIfLarger({self.max_size}) of {H}x{W} to {p.resized[0]}x{p.resized[1]}: ratio in/out above {MAX_RATIO} "
+                    f"(at most {MAX_TAPS} taps)")
+        a = p.angle % 360.0
+        if not (a == 0 or a <= MAX_ANGLE or a >= 360.0 - MAX_ANGLE):
+            return f"RandomRotate by {p.angle:.3f} degrees: |angle| above {MAX_ANGLE:g}"
+        return None
+
+    def warp_plan(self, size, p: SampleParams):
+        """The passes of the aerial geometry for one sample, in order: a list of dicts with ``H``, ``W`` (the pass's source),
+        ``out_h``, ``out_w`` and ``resize=True`` or ``a`` / ``flip`` / ``fill`` (see warp_descs)."""
+        H, W = size
+        plan = []
+        if p.resized is not None:
+            if tuple(p.resized) != resize_if_larger(H, W, self.max_size):
+                raise ValueError(f"DeviceAugment: SampleParams.resized {p.resized} is not ResizeIfLarger({self.max_size}) of {H}x{W}")
+            plan.append(dict(H=H, W=W, out_h=p.resized[0], out_w=p.resized[1], resize=True))
+            H, W = p.resized
+        flip = (FLIP_X if p.flip else 0) | (FLIP_Y if p.vflip else 0)
+        plan.append(dict(H=H, W=W, out_h=H, out_w=W, a=(1, 0, p.dx, 0, 1, p.dy), flip=flip, fill=self.ignore_label))
+        rot = rotate_matrix(W, H, p.angle)
+        if rot is not None:
+            plan.append(dict(H=H, W=W, out_h=rot[2], out_w=rot[1], a=rot[0], flip=0, fill=self.ignore_label))
+            H, W = rot[2], rot[1]
+        if (H, W) != tuple(p.warped):
+            raise ValueError(f"DeviceAugment: SampleParams.warped {p.warped} does not follow from the sample's geometry ({H}, {W})")
+        return plan
 
     # ------------------------------------------------------------------ tables
 
@@ -243,10 +599,12 @@ class DeviceAugment(object):
         return (im * 255).astype(np.uint8)
 
     def _sample_tables(self, size, p: SampleParams):
+        """``size``: what RandomScale resizes (_scale_source).  With the aerial geometry the flip is already in the translate pass."""
         H, W = size
+        flip = p.flip and not self.aerial
         if p.cutout is not None and not (0 <= p.cutout[0] <= self.th - self.cutout_size and 0 <= p.cutout[1] <= self.tw - self.cutout_size):
             raise ValueError("DeviceAugment: cutout square outside the crop")
-        ct, lc = self._window(self._axis(W, p.w), W, p.w, p.sw, self.tw, p.flip)
+        ct, lc = self._window(self._axis(W, p.w), W, p.w, p.sw, self.tw, flip)
         rt, lr = self._window(self._axis(H, p.h), H, p.h, p.sh, self.th, False)
         tile = np.arange(0, self.th, TILE_ROWS)
         span = np.maximum.reduceat(rt["first"] + np.maximum(rt["n"], 1) - 1, tile) - np.minimum.reduceat(rt["first"], tile) + 1
@@ -260,9 +618,14 @@ class DeviceAugment(object):
         taps = pad_y = pad_x = 0
         for i, (s, p) in enumerate(zip(sizes, params)):
             ok, t, py, px = self._limits(s, p)
+            why = self._warp_refusal(s, p)
+            if why is not None:
+                raise RuntimeError(f"DeviceAugment: sample {i} (source {s[0]}x{s[1]}) is outside coverage: {why}")
             if not ok:
+                s = self._scale_source(s, p)
+                step = "padding: RandomCrop's reflect pad >= the resized size" if t and t <= MAX_TAPS else "RandomScale: ratio above 2.5"
                 raise RuntimeError(f"DeviceAugment: sample {i} (source {s[0]}x{s[1]}, resized {p.h}x{p.w}, crop {self.th}x{self.tw}) is "
-                                   f"outside coverage: a resize ratio in/out <= {MAX_RATIO} per axis (scale >= 0.4, at most "
+                                   f"outside coverage ({step}): a resize ratio in/out <= {MAX_RATIO} per axis (scale >= 0.4, at most "
                                    f"{MAX_TAPS} taps) and padding <= resized size - 1")
             taps, pad_y, pad_x = max(taps, t), max(pad_y, py), max(pad_x, px)
         return taps, pad_y, pad_x, min(p.h for p in params), min(p.w for p in params)
@@ -325,9 +688,14 @@ class DeviceAugment(object):
         dev = images[0].device
         images = [t.contiguous() for t in images]
         labels = [t.contiguous() for t in labels]
+        im_ptrs, lb_ptrs = [t.data_ptr() for t in images], [t.data_ptr() for t in labels]
+        if self.aerial:
+            with torch.cuda.device(dev):
+                im_ptrs, lb_ptrs = self._device_warp(lib, dev, im_ptrs, lb_ptrs, sizes, params)
+            sizes = [self._scale_source(s, p) for s, p in zip(sizes, params)]
         if not lib.cabinet_augment_supported(th, tw, *limits):   # the batch's own figures: the library's word on coverage
             _lib.check(-2, "cabinet_augment_supported")
-        table = torch.from_numpy(self.build_table([t.data_ptr() for t in images], [t.data_ptr() for t in labels], sizes, params)).to(dev)
+        table = torch.from_numpy(self.build_table(im_ptrs, lb_ptrs, sizes, params)).to(dev)
         need = int(lib.cabinet_augment_workspace_bytes(N, th, tw))
         ws = torch.empty(need, dtype=torch.uint8, device=dev)  # from torch's stream-ordered cache: no device allocation per call
         u8 = torch.empty((N, th, tw, 3), dtype=torch.uint8, device=dev) if return_uint8 else None
@@ -340,6 +708,51 @@ class DeviceAugment(object):
         _lib.check(rc, "cabinet_augment_batch")
         return u8
 
+    def _buffer(self, dev, name, nbytes):
+        """A cached, grow-only uint8 device buffer: the passes of consecutive calls on one stream reuse it in stream order."""
+        buf = self._buffers.get((dev, name))
+        if buf is None or buf.numel() < nbytes:
+            buf = self._buffers[(dev, name)] = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
+        return buf
+
+    def warp_stages(self, dev, im_ptrs, lb_ptrs, sizes, params):
+        """The launches of the aerial geometry for a batch: resize where ResizeIfLarger acts, translate with the flips, rotate
+        where the angle is no copy -- at most one launch per pass for the whole batch, into cached device buffers.  Returns
+        ([(pass name, entry point name, descriptor block on the device, count, max_out_h, max_out_w, items)], image addresses,
+        label addresses): the addresses of each sample's warped image and label."""
+        plans = [self.warp_plan(s, p) for s, p in zip(sizes, params)]
+        im_ptrs, lb_ptrs = list(im_ptrs), list(lb_ptrs)
+        translate = lambda st: "a" in st and st["a"][1] == 0 and st["a"][3] == 0  # noqa: E731
+        passes = (("resize", lambda st: st.get("resize"), "cabinet_augment_resize_batch"), ("translate", translate, "cabinet_augment_warp_batch"),
+                  ("rotate", lambda st: "a" in st and not translate(st), "cabinet_augment_warp_batch"))
+        stages = []
+        for name, mine, entry in passes:
+            todo = [(i, st) for i, plan in enumerate(plans) for st in plan if mine(st)]
+            if not todo:
+                continue
+            base = self._buffer(dev, name, sum(4 * st["out_h"] * st["out_w"] for _, st in todo)).data_ptr()
+            items, off = [], 0
+            for i, st in todo:
+                px = st["out_h"] * st["out_w"]
+                items.append(dict(st, src_image=im_ptrs[i], src_label=lb_ptrs[i], dst_image=base + off, dst_label=base + off + 3 * px))
+                im_ptrs[i], lb_ptrs[i] = base + off, base + off + 3 * px
+                off += 4 * px
+            descs = torch.from_numpy(warp_descs(items)).to(dev)
+            stages.append((name, entry, descs, len(items), max(st["out_h"] for _, st in todo), max(st["out_w"] for _, st in todo), items))
+        return stages, im_ptrs, lb_ptrs
+
+    def _device_warp(self, lib, dev, im_ptrs, lb_ptrs, sizes, params):
+        """Runs warp_stages on the current stream; the library's word on coverage first."""
+        for s, p in zip(sizes, params):
+            ratio = max(s[0] / p.resized[0], s[1] / p.resized[1]) if p.resized is not None else 0.0
+            if not lib.cabinet_augment_warp_supported(s[0], s[1], p.warped[0], p.warped[1], float(p.angle), float(ratio)):
+                _lib.check(-2, "cabinet_augment_warp_supported")
+        stages, im_ptrs, lb_ptrs = self.warp_stages(dev, im_ptrs, lb_ptrs, sizes, params)
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        for _, entry, descs, n, max_h, max_w, _ in stages:
+            _lib.check(getattr(lib, entry)(descs.data_ptr(), n, max_h, max_w, stream), entry)
+        return im_ptrs, lb_ptrs
+
     def build_table(self, image_ptrs, label_ptrs, sizes, params) -> np.ndarray:
         """The batch's device table as host bytes (include/cabinet_hip.h, cabinet_augment_batch): N entries, then each sample's
         column taps, row taps, label column and label row indices, 16-byte aligned, named by byte offset."""
@@ -347,7 +760,9 @@ class DeviceAugment(object):
         a16 = lambda v: (v + 15) & ~15  # noqa: E731
         per = a16(tw * 32) + a16(th * 32) + a16(tw * 4) + a16(th * 4)
         head = a16(N * SAMPLE_DTYPE.itemsize)
-        blob = np.zeros(head + N * per, dtype=np.uint8)
+        hsv_at = head + N * per   # the 768-byte H, S, V tables of the samples with RandomHSV, behind everything else
+        n_hsv = sum(p.hsv is not None for p in params)
+        blob = np.zeros(hsv_at + n_hsv * 768, dtype=np.uint8)
         entries = blob[:N * SAMPLE_DTYPE.itemsize].view(SAMPLE_DTYPE)
         for i, (size, p) in enumerate(zip(sizes, params)):
             ct, rt, lc, lr = self._sample_tables(size, p)
@@ -360,6 +775,11 @@ class DeviceAugment(object):
                 e[name] = off
                 off += a16(raw.size)
             self._fill_entry(e, p)
+            if p.hsv is not None:
+                blob[hsv_at:hsv_at + 768] = hsv_tables(*p.hsv).reshape(-1)
+                e["flags"] |= FLAG_HSV
+                e["reserved"] = hsv_at
+                hsv_at += 768
         return blob
 
     def _fill_entry(self, e, p: SampleParams):
@@ -406,7 +826,22 @@ class DeviceAugment(object):
             return t.astype(np.uint8)
         return np.where(t <= 0, 0, np.where(t >= 255, 255, np.clip(t, 0, 255).astype(np.uint8))).astype(np.uint8)
 
+    def _host_warp(self, image, label, size, p: SampleParams):
+        """The aerial geometry in numpy, pass by pass as the device runs it (warp_plan)."""
+        for st in self.warp_plan(size, p):
+            if st.get("resize"):
+                (ct, lc), (rt, lr) = _resize_axis(st["W"], st["out_w"]), _resize_axis(st["H"], st["out_h"])
+                image = self._apply_taps(self._apply_taps(image, ct, 1), rt, 0)
+                label = label[lr[:, None], lc[None, :]]
+            else:
+                image, label = (affine_image(image, st["a"], st["out_w"], st["out_h"], st["flip"]),
+                                affine_label(label, st["a"], st["out_w"], st["out_h"], st["fill"], st["flip"]))
+        return image, label
+
     def _host_sample(self, image, label, size, p: SampleParams, noise, seed, index):
+        if self.aerial:
+            image, label = self._host_warp(image, label, size, p)
+            size = self._scale_source(size, p)
         ct, rt, lc, lr = self._sample_tables(size, p)
         used = np.zeros(size[0], dtype=bool)   # the horizontal pass runs over the source rows the vertical one reads
         for k in range(MAX_TAPS):
@@ -419,6 +854,8 @@ class DeviceAugment(object):
         # taps of one output row are consecutive source rows, all of them used: their positions in `rows` are consecutive too
         rt2["first"] = remap[np.clip(rt["first"], 0, size[0] - 1)]
         im = self._apply_taps(hor, rt2, 0)
+        if p.hsv is not None:
+            im = apply_hsv(im, hsv_tables(*p.hsv))
         lb = np.where((lr[:, None] < 0) | (lc[None, :] < 0), -1, 0)
         src_lb = label[np.clip(lr, 0, None)[:, None], np.clip(lc, 0, None)[None, :]]
         lb = np.where(lb < 0, self.ignore_label, self.label_lut[src_lb]).astype(np.int64)

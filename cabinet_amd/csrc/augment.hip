@@ -19,26 +19,19 @@
 
 #include "../../include/cabinet_hip.h"
 #include "common.hpp"
+#include "augment_taps.hpp"
 
 namespace cabinet {
 
-#define AUG_TX 64   // tile columns
-#define AUG_TY 16   // tile rows
-#define AUG_RS 48   // source rows a tile can need: fewer than (AUG_TY + 1) * 2.5 + 1 = 43.5 at the widest resize ratio, 2.5; rounded up
-#define AUG_TAPS 5
-
 typedef cabinet_augment_sample AugSample;
-typedef cabinet_augment_tap AugTap;
 
-static_assert(sizeof(AugTap) == 32 && sizeof(AugSample) == 2400, "table layout (include/cabinet_hip.h, cabinet_amd/augment.py)");
+static_assert(sizeof(AugSample) == 2400, "table layout (include/cabinet_hip.h, cabinet_amd/augment.py)");
 
 int augment_tiles(int th, int tw) { return ceil_div(th, AUG_TY) * ceil_div(tw, AUG_TX); }
 static size_t augment_crop_stride(int th, int tw) { return align_up((size_t)th * tw * 3, 16); }
 size_t augment_workspace(int N, int th, int tw) {
     return align_up((size_t)N * augment_crop_stride(th, tw), 256) + (size_t)N * augment_tiles(th, tw) * sizeof(unsigned long long);
 }
-
-__device__ __forceinline__ int clip8(int v) { return min(max(v, 0), 255); }
 
 // Pillow's L of an RGB pixel
 __device__ __forceinline__ int luma(int r, int g, int b) { return (19595 * r + 38470 * g + 7471 * b + 0x8000) >> 16; }
@@ -50,13 +43,46 @@ __device__ __forceinline__ int blend8(int deg, int src, float r, bool inside) {
     return t <= 0.f ? 0 : (t >= 255.f ? 255 : (int)t);
 }
 
-// a tap as the kernels use it: at most AUG_TAPS of them, all inside [0, size)
-__device__ __forceinline__ AugTap load_tap(const AugTap* p, int size) {
-    AugTap t = *p;
-    t.n = min(max(t.n, 0), AUG_TAPS);
-    t.first = min(max(t.first, 0), size - 1);
-    t.step = t.step < 0 ? -1 : 1;
-    return t;
+// RandomHSV on one pixel (K20): Pillow's RGB -> HSV bytes, the three byte tables (H at 0, S at 256, V at 512), Pillow's HSV -> RGB.
+// fp32 where Pillow's C uses float, double where its expressions promote; every operation rounded on its own.
+__device__ __forceinline__ void hsv_pixel(const unsigned char* __restrict__ lut, int (&px)[3]) {
+    const int r = px[0], g = px[1], b = px[2];
+    const int maxc = max(r, max(g, b)), minc = min(r, min(g, b));
+    int h8 = 0, s8 = 0;
+    if (maxc != minc) {
+        const float cr = (float)(maxc - minc);
+        const float s = __fdiv_rn(cr, (float)maxc);
+        const float rc = __fdiv_rn((float)(maxc - r), cr), gc = __fdiv_rn((float)(maxc - g), cr), bc = __fdiv_rn((float)(maxc - b), cr);
+        float h;
+        if (r == maxc) h = __fsub_rn(bc, gc);
+        else if (g == maxc) h = (float)__dsub_rn(__dadd_rn(2.0, (double)rc), (double)bc);
+        else h = (float)__dsub_rn(__dadd_rn(4.0, (double)gc), (double)rc);
+        const double u = __dadd_rn(__ddiv_rn((double)h, 6.0), 1.0);  // in (0.8, 2): fmod(u, 1) = u - floor(u), exact
+        h = (float)__dsub_rn(u, floor(u));
+        h8 = clip8((int)__dmul_rn((double)h, 255.0));
+        s8 = clip8((int)__dmul_rn((double)s, 255.0));
+    }
+    const int H = lut[h8], S = lut[256 + s8], V = lut[512 + maxc];
+    if (S == 0) {
+        px[0] = px[1] = px[2] = V;
+        return;
+    }
+    const double hh = __ddiv_rn(__dmul_rn((double)H, 6.0), 255.0);
+    const double fl = floor(hh);
+    const float f = (float)__dsub_rn(hh, fl);
+    const float fs = (float)__ddiv_rn((double)S, 255.0);
+    const double v = (double)V;
+    const int p = clip8((int)round(__dmul_rn(v, __dsub_rn(1.0, (double)fs))));
+    const int q = clip8((int)round(__dmul_rn(v, __dsub_rn(1.0, __dmul_rn((double)fs, (double)f)))));
+    const int tt = clip8((int)round(__dmul_rn(v, __dsub_rn(1.0, __dmul_rn((double)fs, __dsub_rn(1.0, (double)f))))));
+    switch ((int)fl % 6) {
+        case 0: px[0] = V, px[1] = tt, px[2] = p; break;
+        case 1: px[0] = q, px[1] = V, px[2] = p; break;
+        case 2: px[0] = p, px[1] = V, px[2] = tt; break;
+        case 3: px[0] = p, px[1] = q, px[2] = V; break;
+        case 4: px[0] = tt, px[1] = p, px[2] = V; break;
+        default: px[0] = V, px[1] = p, px[2] = q; break;
+    }
 }
 
 __global__ __launch_bounds__(256) void augment_geom_kernel(const unsigned char* __restrict__ table, int th, int tw,
@@ -65,6 +91,7 @@ __global__ __launch_bounds__(256) void augment_geom_kernel(const unsigned char* 
     __shared__ unsigned char hrow[AUG_RS][AUG_TX * 3];
     __shared__ AugTap rtap[AUG_TY];
     __shared__ unsigned red[4];
+    __shared__ unsigned char hsvt[768];  // RandomHSV's H, S and V byte tables (CABINET_AUGMENT_HSV)
     const int t = threadIdx.x, n = blockIdx.z;
     const int x0 = blockIdx.x * AUG_TX, y0 = blockIdx.y * AUG_TY;
     const AugSample* S = reinterpret_cast<const AugSample*>(table) + n;
@@ -74,29 +101,21 @@ __global__ __launch_bounds__(256) void augment_geom_kernel(const unsigned char* 
     const AugTap* col_taps = reinterpret_cast<const AugTap*>(table + S->col_taps);
     const int rows = min(AUG_TY, th - y0);
     if (t < rows) rtap[t] = load_tap(row_taps + y0 + t, H);
-    __syncthreads();
-    int lo = H - 1, hi = 0;  // source rows this tile reads
-    for (int j = 0; j < rows; ++j) {
-        const int a = rtap[j].first, b = min(max(a + rtap[j].step * (max(rtap[j].n, 1) - 1), 0), H - 1);
-        lo = min(lo, min(a, b)), hi = max(hi, max(a, b));
+    const bool hsv = (S->flags & CABINET_AUGMENT_HSV) != 0;  // uniform per sample: a scalar branch
+    if (hsv) {
+        const unsigned char* g = table + (size_t)max(S->reserved, 0);
+        for (int i = t; i < 768; i += 256) hsvt[i] = g[i];
     }
-    const int span = min(hi - lo + 1, AUG_RS);  // the clamp is for memory safety alone: coverage (in/out <= 2.5) keeps hi - lo + 1 <= 43
+    __syncthreads();
+    int lo, span;  // source rows this tile reads; coverage (in/out <= 2.5) keeps the span <= 43
+    tap_rows_span(rtap, rows, H, lo, span);
 
     const int col = t & (AUG_TX - 1), x = x0 + col;
     const bool live = x < tw;
     if (live) {  // horizontal pass: source rows lo .. lo + span - 1 at this thread's column
         const AugTap c = load_tap(col_taps + x, W);
         for (int r = t >> 6; r < span; r += 4) {
-            const unsigned char* src = img + (size_t)(lo + r) * W * 3;
-            int acc[3] = {1 << 21, 1 << 21, 1 << 21};
-#pragma unroll
-            for (int k = 0; k < AUG_TAPS; ++k)
-                if (k < c.n) {
-                    const unsigned char* p = src + (size_t)min(max(c.first + c.step * k, 0), W - 1) * 3;
-                    acc[0] += c.coef[k] * (int)p[0], acc[1] += c.coef[k] * (int)p[1], acc[2] += c.coef[k] * (int)p[2];
-                }
-#pragma unroll
-            for (int ch = 0; ch < 3; ++ch) hrow[r][col * 3 + ch] = (unsigned char)clip8(acc[ch] >> 22);
+            tap_horizontal(img + (size_t)(lo + r) * W * 3, c, W, &hrow[r][col * 3]);
         }
     }
     __syncthreads();
@@ -111,16 +130,11 @@ __global__ __launch_bounds__(256) void augment_geom_kernel(const unsigned char* 
         for (int j = t >> 6; j < rows; j += 4) {
             const int y = y0 + j;
             const AugTap v = rtap[j];
-            int acc[3] = {1 << 21, 1 << 21, 1 << 21};
-#pragma unroll
-            for (int k = 0; k < AUG_TAPS; ++k)
-                if (k < v.n) {
-                    const unsigned char* p = &hrow[min(max(v.first + v.step * k - lo, 0), span - 1)][col * 3];
-                    acc[0] += v.coef[k] * (int)p[0], acc[1] += v.coef[k] * (int)p[1], acc[2] += v.coef[k] * (int)p[2];
-                }
             int px[3];
+            tap_vertical(hrow, col * 3, v, lo, span, px);
+            if (hsv) hsv_pixel(hsvt, px);
 #pragma unroll
-            for (int ch = 0; ch < 3; ++ch) px[ch] = blend8(0, clip8(acc[ch] >> 22), rb, inside);
+            for (int ch = 0; ch < 3; ++ch) px[ch] = blend8(0, px[ch], rb, inside);
             sum += (unsigned)luma(px[0], px[1], px[2]);
             unsigned char* o = crop + (size_t)n * crop_stride + ((size_t)y * tw + x) * 3;
             o[0] = (unsigned char)px[0], o[1] = (unsigned char)px[1], o[2] = (unsigned char)px[2];

@@ -187,6 +187,9 @@ hipError_t predict_argmax_run(const float* total, int N, int C, int H, int W, un
 hipError_t predict_render_run(const unsigned char* labels, const float* image, const unsigned char* palette, int n_colors,
                               const float* mean, const float* std, float alpha, int N, int H, int W, unsigned char* pred,
                               unsigned char* inp, unsigned char* ovl, hipStream_t stream);
+// augment_warp.hip
+hipError_t augment_warp_run(const void* descs, int N, int max_oh, int max_ow, hipStream_t stream);
+hipError_t augment_resize_run(const void* descs, int N, int max_oh, int max_ow, hipStream_t stream);
 // augment.hip
 size_t augment_workspace(int N, int th, int tw);
 hipError_t augment_run(const void* samples, int N, int th, int tw, const float* noise, unsigned long long seed, const float* mean,
@@ -1590,6 +1593,40 @@ int cabinet_augment_batch(const void* samples, int N, int th, int tw, const floa
     return hip_status(cabinet::augment_run(samples, N, th, tw, noise, seed, mean, std, out_image, out_label, out_u8, workspace,
                                            static_cast<hipStream_t>(stream)),
                       "augment_batch launch");
+}
+
+// ------------------------------------------------------ aerial augmentation (K20): resize, flips + translate, rotate as uint8 passes
+int cabinet_augment_warp_supported(int H, int W, int out_h, int out_w, double angle_deg, double resize_ratio) {
+    if (H < 1 || W < 1 || out_h < 1 || out_w < 1 || H > 32768 || W > 32768 || out_h > 32768 || out_w > 32768)
+        return fail(0, "augment_warp: source %d x %d or output %d x %d outside [1, 32768]", H, W, out_h, out_w);
+    double a = fmod(angle_deg, 360.0);  // NaN stays NaN and fails the comparison below
+    if (a > 180.0) a -= 360.0;
+    if (a <= -180.0) a += 360.0;
+    if (!(fabs(a) <= 45.0)) return fail(0, "augment_warp: RandomRotate by %g degrees (the rotation pass covers |angle| <= 45)", angle_deg);
+    if (!(resize_ratio >= 0.0 && resize_ratio <= 2.5))
+        return fail(0, "augment_warp: ResizeIfLarger ratio in/out %g (at most 2.5: five taps, 48 staged rows per tile)", resize_ratio);
+    return 1;
+}
+
+static int warp_args(const char* who, const void* descs, int N, int max_out_h, int max_out_w) {
+    if (!descs) return fail(CABINET_ERR_INVALID_ARG, "%s: null descs", who);
+    if (N <= 0 || max_out_h <= 0 || max_out_w <= 0) return fail(CABINET_ERR_INVALID_ARG, "%s: non-positive dimension", who);
+    if (reinterpret_cast<uintptr_t>(descs) & 7) return fail(CABINET_ERR_INVALID_ARG, "%s: descs must be 8-byte aligned", who);
+    if (max_out_h > 32768 || max_out_w > 32768) return fail(CABINET_ERR_UNSUPPORTED, "%s: output %d x %d above 32768", who, max_out_h, max_out_w);
+    if (N > 65535) return fail(CABINET_ERR_UNSUPPORTED, "%s: N=%d exceeds grid limits", who, N);
+    return CABINET_OK;
+}
+
+int cabinet_augment_warp_batch(const void* descs, int N, int max_out_h, int max_out_w, cabinet_stream_t stream) {
+    const int rc = warp_args("augment_warp_batch", descs, N, max_out_h, max_out_w);
+    if (rc != CABINET_OK) return rc;
+    return hip_status(cabinet::augment_warp_run(descs, N, max_out_h, max_out_w, static_cast<hipStream_t>(stream)), "augment_warp_batch launch");
+}
+
+int cabinet_augment_resize_batch(const void* descs, int N, int max_out_h, int max_out_w, cabinet_stream_t stream) {
+    const int rc = warp_args("augment_resize_batch", descs, N, max_out_h, max_out_w);
+    if (rc != CABINET_OK) return rc;
+    return hip_status(cabinet::augment_resize_run(descs, N, max_out_h, max_out_w, static_cast<hipStream_t>(stream)), "augment_resize_batch launch");
 }
 
 }  // extern "C"

@@ -875,6 +875,72 @@ int cabinet_augment_batch(const void* samples, int N, int th, int tw, const floa
                           const float* mean, const float* std, float* out_image, long long* out_label, unsigned char* out_u8,
                           void* workspace, size_t workspace_bytes, cabinet_stream_t stream);
 
+/* ------------------------------------------------------------------------- *
+ * Aerial-dataset augmentation (K20; ADDITIVE to ABI version 8).  What the train pipeline shared by src/datasets/uavid.py
+ * (:192-230), vdd.py and aeroscapes.py does ahead of RandomScale -- ResizeIfLarger, RandomHorizontalFlip, RandomVerticalFlip,
+ * RandomTranslate, RandomRotate(expand=True) of src/datasets/transform.py -- as batched passes from uint8 to uint8 (Pillow
+ * truncates to bytes between the steps), and RandomHSV inside cabinet_augment_batch.  One launch per call on `stream`; nothing
+ * is allocated, nothing synchronises.
+ *
+ * RandomHSV: flag CABINET_AUGMENT_HSV in cabinet_augment_sample.flags; `reserved` is then the BYTE OFFSET from `samples` of 768
+ * bytes: the H, S and V byte tables (the caller builds them with the reference's numpy expressions).  Each pixel of the crop,
+ * after the resample and ahead of the brightness blend (so the contrast blend's mean luma is that of the converted crop), goes
+ * RGB -> HSV bytes (Pillow's rgb2hsv), through the tables, and HSV -> RGB bytes (Pillow's hsv2rgb).  Flag clear: `reserved` is
+ * not read, and 0 as before.
+ *
+ * descs: DEVICE memory, 8-byte aligned: N entries of cabinet_augment_warp_desc, then the tables they name by BYTE OFFSET from
+ * `descs` (4-byte aligned).  Image arrays are (rows, cols, 3) uint8 interleaved, label arrays (rows, cols) uint8, any alignment;
+ * a pass writes EVERY byte of dst_image (out_h, out_w, 3) and dst_label (out_h, out_w), fill included, and no other byte; every
+ * source index is clamped into [0, H) x [0, W) where it is used.  Samples of a batch may differ in every size: the grid is sized
+ * by max_out_h x max_out_w, which must be >= every entry's out_h x out_w.
+ *
+ * cabinet_augment_warp_batch -- Pillow's Image.transform(size, AFFINE, a, BILINEAR) for the image and (..., NEAREST,
+ * fillcolor=fill) for the label.  The source is read through `flip` (bit 0: columns mirrored, bit 1: rows mirrored), i.e. the
+ * pass transforms the flipped source.  Image, output pixel (x, y), in double with every operation rounded on its own:
+ *     xin = a[0] (x + 0.5) + a[1] (y + 0.5) + a[2],  yin = a[3] (x + 0.5) + a[4] (y + 0.5) + a[5]   (left to right)
+ *   outside 0 <= xin < W, 0 <= yin < H the pixel is 0; otherwise with xs = xin - 0.5, xf = floor(xs), dx = xs - xf (y likewise),
+ *   columns clamp(xf), clamp(xf + 1), row clamp(yf): v1 = p00 + (p01 - p00) dx; v2 the same from row yf + 1 if it is inside,
+ *   else v1; byte = (uint8)(v1 + (v2 - v1) dy), truncated.
+ *   Label, label_mode CABINET_WARP_LABEL_TABLES (a[1] == a[3] == 0; Pillow builds per-axis tables by a running sum): lab_col
+ *   [out_w] and lab_row [out_h] int32 at byte offsets, the source index or -1; both >= 0: the source byte, else `fill`.
+ *   label_mode CABINET_WARP_LABEL_FIXED (Pillow's 16.16 fixed point): column (fix[2] + y fix[1] + x fix[0]) >> 16, row
+ *   (fix[5] + y fix[4] + x fix[3]) >> 16, arithmetic shifts of 64-bit integers; both inside the source: its byte, else `fill`.
+ *   The caller computes fix[] as FIX(v) = floor(v 65536 + 0.5) of a[0], a[1], a[2] + a[0]/2 + a[1]/2, a[3], a[4], a[5] + a[3]/2 + a[4]/2.
+ *
+ * cabinet_augment_resize_batch -- Pillow's resize: BILINEAR for the image through col_taps[out_w], row_taps[out_h] of
+ * cabinet_augment_tap (horizontal pass into a uint8 intermediate, then vertical; the arithmetic and the tile contract of
+ * cabinet_augment_batch: <= 5 taps, <= 48 source rows under 16 consecutive output rows, i.e. ratio in/out <= 2.5), NEAREST for
+ * the label through lab_col, lab_row (clamped into the source; no fill).  a, fix, flip, label_mode and fill are not read.
+ *
+ * Return codes: -1 for null descs, N <= 0, a non-positive max size or descs not 8-byte aligned; -2 for a max size above 32768 or
+ * N above 65535 -- all before any HIP call.  cabinet_augment_warp_supported answers 1 / 0 (reason in cabinet_last_error()) for
+ * one sample's figures: sizes in [1, 32768]; angle_deg (rotation, 0 for none) exactly 0 or 0 < |angle| <= 45 after reduction to
+ * (-180, 180]; resize_ratio (ResizeIfLarger's in/out, 0 for none) <= 2.5.
+ * ------------------------------------------------------------------------- */
+#define CABINET_AUGMENT_HSV 16
+
+#define CABINET_WARP_LABEL_TABLES 0
+#define CABINET_WARP_LABEL_FIXED 1
+#define CABINET_WARP_FLIP_X 1
+#define CABINET_WARP_FLIP_Y 2
+
+typedef struct cabinet_augment_warp_desc {
+    const unsigned char* src_image;
+    const unsigned char* src_label;
+    unsigned char* dst_image;
+    unsigned char* dst_label;
+    int H, W;                                                /* source */
+    int out_h, out_w;
+    double a[6];
+    long long fix[6];
+    unsigned long long lab_col, lab_row, col_taps, row_taps; /* byte offsets from `descs` */
+    int flip, label_mode, fill, reserved;
+} cabinet_augment_warp_desc; /* 192 bytes */
+
+int cabinet_augment_warp_supported(int H, int W, int out_h, int out_w, double angle_deg, double resize_ratio);
+int cabinet_augment_warp_batch(const void* descs, int N, int max_out_h, int max_out_w, cabinet_stream_t stream);
+int cabinet_augment_resize_batch(const void* descs, int N, int max_out_h, int max_out_w, cabinet_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
