@@ -17,7 +17,9 @@
 // as its tensor's base pointers.  A tensor of <= 4096 elements is ONE chunk of its own (the 144 tiny tensors of CABiNet-Large are
 // 144 of ~2,700 chunks: packing several per workgroup would save ~5 % of the workgroups' iterations and cost a second index level).
 // Where the pointers a pass touches are 16-byte aligned the body of the chunk moves as float4 and the last numel % 4 elements as
-// scalars; otherwise the whole chunk moves as scalars.  Nothing here allocates, synchronises or reads on the host.
+// scalars; otherwise the whole chunk moves as scalars -- in the norm pass element for element in the float4 form's order, so that
+// neither the norm nor anything derived from it depends on where a gradient starts.  Nothing here allocates, synchronises or reads
+// on the host.
 #include "../../include/cabinet_hip.h"
 #include "common.hpp"
 
@@ -65,7 +67,10 @@ __global__ __launch_bounds__(TAIL_THREADS) void sgd_tail_norm(const cabinet_sgd_
         if (live && !(e.flags & CABINET_SGD_TAIL_EMA_ONLY) && e.grad) {
             const float* g = e.grad + ck.start;
             const int len = ck.length;
-            const int nvec = ptr_aligned16(g, nullptr, nullptr, nullptr) ? (len >> 2) : 0;
+            // the same elements in the same order whether or not the gradient is 16-byte aligned (then four dword loads stand
+            // for the float4): the norm, and with it the clip coefficient, has the same bits for any address of the gradient
+            const bool vec = ptr_aligned16(g, nullptr, nullptr, nullptr);
+            const int nvec = len >> 2;
             const float4* g4 = reinterpret_cast<const float4*>(g);
             // 4 independent accumulators: vector v of the chunk goes to accumulator (v / 256) & 3
             float4 x[4];
@@ -73,13 +78,13 @@ __global__ __launch_bounds__(TAIL_THREADS) void sgd_tail_norm(const cabinet_sgd_
             for (int j = 0; j < 4; ++j) {
                 const int v = j * TAIL_THREADS + t;
                 x[j] = make_float4(0.f, 0.f, 0.f, 0.f);
-                if (v < nvec) x[j] = g4[v];
+                if (v < nvec) x[j] = vec ? g4[v] : make_float4(g[4 * v], g[4 * v + 1], g[4 * v + 2], g[4 * v + 3]);
             }
             a0 = (x[0].x * x[0].x + x[0].y * x[0].y) + (x[0].z * x[0].z + x[0].w * x[0].w);
             a1 = (x[1].x * x[1].x + x[1].y * x[1].y) + (x[1].z * x[1].z + x[1].w * x[1].w);
             a2 = (x[2].x * x[2].x + x[2].y * x[2].y) + (x[2].z * x[2].z + x[2].w * x[2].w);
             a3 = (x[3].x * x[3].x + x[3].y * x[3].y) + (x[3].z * x[3].z + x[3].w * x[3].w);
-            // scalar path: the whole chunk when the gradient is not 16-byte aligned, else the last length % 4 elements
+            // the last length % 4 elements
             float s[4] = {0.f, 0.f, 0.f, 0.f};
             int j = 0;
             for (int i = nvec * 4 + t; i < len; i += TAIL_THREADS, ++j) {

@@ -78,9 +78,14 @@ def instrument(net):
     # the FFM's pre-BatchNorm product and saved statistics (round 6): what its kernels decide their ReLU mask on
     _FFM_REGISTRY[id(net.ffm.convblk.conv.weight)] = cap
     _install_ffm_spy()
+    # the registries outlive this model (the spies stay installed for the process): their keys stay alive with them, so that no
+    # later model's weight can be given the id of one of these and be routed into `cap`
+    _REGISTERED[:] = [net.ab.conva[0].weight, net.ab.b1.weight, net.conv_out.conv.conv.weight, net.ab.b4.weight,
+                      net.conv_out.conv_out.weight, net.ffm.convblk.conv.weight]
     return cap
 
 
+_REGISTERED = []
 _FFM_REGISTRY = {}
 
 
