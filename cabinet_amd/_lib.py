@@ -135,6 +135,9 @@ SIGNATURES = {
     "cabinet_sgd_tail_workspace_bytes": (_SZ, [_INT]),
     "cabinet_sgd_tail_state_bytes": (_SZ, [_INT]),
     "cabinet_sgd_tail_step": (_INT, [_PTR, _INT, _PTR, _INT, _PTR, _PTR, _SZ, _INT, _PTR, _SZ, _PTR]),
+    "cabinet_grad_accum_state_bytes": (_SZ, []),
+    "cabinet_grad_accum": (_INT, [_PTR, _INT, _PTR, _INT, _PTR, _SZ, _INT, _PTR]),
+    "cabinet_grad_accum_reset": (_INT, [_PTR, _SZ, _PTR]),
     "cabinet_augment_supported": (_INT, [_INT] * 7),
     "cabinet_augment_workspace_bytes": (_SZ, [_INT] * 3),
     "cabinet_augment_batch": (_INT, [_PTR] + [_INT] * 3 + [_PTR, ctypes.c_ulonglong] + [_PTR] * 5 + [_PTR, _SZ, _PTR]),

@@ -200,6 +200,11 @@ size_t sgd_tail_workspace(int n_chunks);
 size_t sgd_tail_state(int n_entries);
 hipError_t sgd_tail_run(const cabinet_sgd_tail_entry* entries, int n_entries, const cabinet_sgd_tail_chunk* chunks, int n_chunks,
                         const cabinet_sgd_tail_config& cfg, void* state, void* ws, int max_grid, hipStream_t stream);
+// grad_accum.hip
+size_t grad_accum_state();
+hipError_t grad_accum_run(const cabinet_grad_accum_entry* entries, int n_entries, const cabinet_sgd_tail_chunk* chunks, int n_chunks,
+                          void* state, int max_grid, hipStream_t stream);
+hipError_t grad_accum_reset_run(void* state, hipStream_t stream);
 }  // namespace cabinet
 
 static thread_local char g_err[512] = "";
@@ -1559,6 +1564,32 @@ int cabinet_sgd_tail_step(const cabinet_sgd_tail_entry* entries, int n_entries, 
     return hip_status(cabinet::sgd_tail_run(entries, n_entries, chunks, n_chunks, *config, state, workspace, max_grid,
                                             static_cast<hipStream_t>(stream)),
                       "sgd_tail_step launch");
+}
+
+// ------------------------------------------------------ gradient accumulation across graph replays (K21)
+size_t cabinet_grad_accum_state_bytes(void) { return cabinet::grad_accum_state(); }
+
+int cabinet_grad_accum(const cabinet_grad_accum_entry* entries, int n_entries, const cabinet_sgd_tail_chunk* chunks, int n_chunks,
+                       void* state, size_t state_bytes, int max_grid, cabinet_stream_t stream) {
+    if (n_entries <= 0 || n_chunks <= 0)
+        return fail(CABINET_ERR_INVALID_ARG, "grad_accum: non-positive count n_entries=%d n_chunks=%d", n_entries, n_chunks);
+    if (!entries || !chunks) return fail(CABINET_ERR_INVALID_ARG, "grad_accum: null table");
+    if (!state) return fail(CABINET_ERR_INVALID_ARG, "grad_accum: null state block");
+    if (max_grid < 0) return fail(CABINET_ERR_INVALID_ARG, "grad_accum: negative max_grid=%d", max_grid);
+    if ((reinterpret_cast<uintptr_t>(entries) | reinterpret_cast<uintptr_t>(chunks) | reinterpret_cast<uintptr_t>(state)) & 7)
+        return fail(CABINET_ERR_INVALID_ARG, "grad_accum: tables and state block must be 8-byte aligned");
+    if (state_bytes < cabinet_grad_accum_state_bytes())
+        return fail(CABINET_ERR_WORKSPACE, "grad_accum: state block %zu < %zu bytes", state_bytes, cabinet_grad_accum_state_bytes());
+    return hip_status(cabinet::grad_accum_run(entries, n_entries, chunks, n_chunks, state, max_grid, static_cast<hipStream_t>(stream)),
+                      "grad_accum launch");
+}
+
+int cabinet_grad_accum_reset(void* state, size_t state_bytes, cabinet_stream_t stream) {
+    if (!state) return fail(CABINET_ERR_INVALID_ARG, "grad_accum_reset: null state block");
+    if (reinterpret_cast<uintptr_t>(state) & 7) return fail(CABINET_ERR_INVALID_ARG, "grad_accum_reset: state block must be 8-byte aligned");
+    if (state_bytes < cabinet_grad_accum_state_bytes())
+        return fail(CABINET_ERR_WORKSPACE, "grad_accum_reset: state block %zu < %zu bytes", state_bytes, cabinet_grad_accum_state_bytes());
+    return hip_status(cabinet::grad_accum_reset_run(state, static_cast<hipStream_t>(stream)), "grad_accum_reset launch");
 }
 
 // ------------------------------------------------------ training augmentation (K18): the reference's Cityscapes transform

@@ -349,3 +349,156 @@ class FusedSGDTail:
                 p.add_(g, alpha=-float(self._scalars[2 + gi]))
             if e is not None:
                 e.mul_(d).add_(p.detach(), alpha=1 - d)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+_ACCUM_ENTRY = np.dtype([("acc", "<u8"), ("grad", "<u8"), ("numel", "<i8")])
+_ACCUM_STATE_BYTES = 64  # micro (int32) | reserved
+
+
+class GradAccumulator:
+    """Gradient accumulation across hipGraph replays as one capturable call (csrc/grad_accum.hip, ``cabinet_grad_accum``).
+
+    ``pairs``: a list of ``(acc, grad)`` tensors.  ``add()`` folds every ``grad`` into its ``acc``: a copy when the device counter
+    ``micro`` is 0 (``acc`` is not read: a stale NaN does not survive), one fp32 add otherwise -- bit for bit what autograd's own
+    accumulation into ``.grad`` gives in the same order -- and advances ``micro``; ``reset()`` sets it to 0.  Nothing is read on the
+    host, so ONE recorded ``add()`` serves every micro-step of every window.  Device tensors use the kernel or raise; host tensors
+    take a composite torch path with the same semantics (what the CPU test tier checks).
+
+    A ``grad`` of ``None`` in EVERY pair leaves the gradient side open: a captured backward only shows its static gradient tensors
+    once it has been recorded, in the capture that also has to record ``add()``.  Recording reads no table, so ``add()`` may be
+    recorded on an open accumulator and ``bind(grads)`` called once, after the capture and before the first replay.  That is the
+    one write into a table a graph holds; afterwards, as in ``FusedSGDTail``, a table a graph has recorded is never overwritten
+    (an address change outside capture uploads a fresh table; inside capture it raises)."""
+
+    def __init__(self, pairs):
+        pairs = [tuple(p) for p in pairs]
+        if not pairs:
+            raise ValueError("GradAccumulator: no tensors")
+        self._acc = [a for a, _ in pairs]
+        grads = [g for _, g in pairs]
+        opened = [g is None for g in grads]
+        if any(opened) and not all(opened):
+            raise ValueError("GradAccumulator: either every pair names its gradient or none does (bind() names them later)")
+        devices = {a.device for a in self._acc}
+        if len(devices) != 1:
+            raise RuntimeError(f"GradAccumulator: tensors on several devices {sorted(map(str, devices))}")
+        self.device = devices.pop()
+        for i, a in enumerate(self._acc):
+            if a.dtype != torch.float32 or not _dense(a):
+                raise RuntimeError(f"GradAccumulator: acc of pair {i} is {a.dtype} {tuple(a.shape)} strides {a.stride()}; the two "
+                                   "tensors of a pair must be dense fp32 with equal strides")
+        self._chunks_host = build_chunks([a.numel() for a in self._acc])
+        if len(self._chunks_host) == 0:
+            raise ValueError("GradAccumulator: every tensor is empty")
+        self._on_device = self.device.type == "cuda"
+        n = len(self._acc)
+        if self._on_device:
+            self._lib = _lib.load()  # a missing library raises here: there is no torch fallback for device tensors
+            state_bytes = int(self._lib.cabinet_grad_accum_state_bytes())
+            self._chunks = torch.from_numpy(self._chunks_host.view(np.uint8)).to(self.device)
+            self._entries = torch.zeros(n * _ACCUM_ENTRY.itemsize, dtype=torch.uint8, device=self.device)
+        else:
+            state_bytes = _ACCUM_STATE_BYTES
+        self._state = torch.zeros(state_bytes, dtype=torch.uint8, device=self.device)
+        self._micro = self._state[0:4].view(torch.int32)
+        self.max_grid = 0                 # 0: the kernel's own cap; tests force the grid-stride loop with a small value
+        self._grad = None                 # bound gradient tensors
+        self._uploaded = None             # the address tuple the device table was built from
+        self._entries_captured = False    # a hipGraph holds the table's address: never overwrite it (but for the one bind())
+        self._keep = []                   # tables held by graphs
+        if not opened[0]:
+            self.bind(grads)
+
+    # ------------------------------------------------------------------ tables
+    def _check_pair(self, i, a, g):
+        if g.dtype != torch.float32 or g.device != a.device or g.shape != a.shape or g.stride() != a.stride():
+            raise RuntimeError(f"GradAccumulator: grad of pair {i} is {g.dtype} {tuple(g.shape)} strides {g.stride()} on "
+                               f"{g.device}; acc is {a.dtype} {tuple(a.shape)} strides {a.stride()} on {a.device}: the two "
+                               "tensors of a pair must be dense fp32 with equal strides")
+        if a.numel() and g.data_ptr() == a.data_ptr():
+            raise RuntimeError(f"GradAccumulator: acc and grad of pair {i} are the same memory")
+
+    def _key(self):
+        return tuple(t.data_ptr() for pair in zip(self._acc, self._grad) for t in pair)
+
+    def _host_table(self):
+        host = np.zeros(len(self._acc), dtype=_ACCUM_ENTRY)
+        for i, (a, g) in enumerate(zip(self._acc, self._grad)):
+            self._check_pair(i, a, g)
+            host[i] = (a.data_ptr(), g.data_ptr(), a.numel())
+        return torch.from_numpy(host.view(np.uint8))
+
+    def bind(self, grads):
+        """Name the gradient side of an open accumulator (once).  Must not be called during stream capture."""
+        if self._grad is not None:
+            raise RuntimeError("GradAccumulator.bind(): the gradients are already bound")
+        grads = list(grads)
+        if len(grads) != len(self._acc):
+            raise RuntimeError(f"GradAccumulator.bind(): {len(grads)} gradients for {len(self._acc)} accumulation tensors")
+        for i, (a, g) in enumerate(zip(self._acc, grads)):
+            self._check_pair(i, a, g)
+        self._grad = grads
+        if self._on_device:
+            self._entries.copy_(self._host_table())  # the table's first content: a recorded add() has not run yet
+            self._uploaded = self._key()
+
+    @property
+    def pairs(self):
+        return list(zip(self._acc, self._grad or [None] * len(self._acc)))
+
+    # ------------------------------------------------------------------ counter
+    @property
+    def micro(self):
+        """Micro-steps folded into ``acc`` in the current window (reads the device: a sync)."""
+        return int(self._micro[0])
+
+    @micro.setter
+    def micro(self, v):
+        self._micro[0] = int(v)
+
+    # ------------------------------------------------------------------ calls
+    def _stream(self):
+        return torch.cuda.current_stream(self.device).cuda_stream
+
+    @torch.no_grad()
+    def add(self):
+        if not self._on_device:
+            if self._grad is None:
+                raise RuntimeError("GradAccumulator.add(): no gradients bound")
+            first = self.micro == 0
+            for i, (a, g) in enumerate(zip(self._acc, self._grad)):
+                self._check_pair(i, a, g)
+                if first:
+                    a.copy_(g)
+                else:
+                    a.add_(g)
+            self._micro[0] += 1
+            return
+        capturing = torch.cuda.is_current_stream_capturing()
+        if self._grad is None:
+            if not capturing:
+                raise RuntimeError("GradAccumulator.add(): no gradients bound; an open accumulator can only be recorded")
+        elif self._key() != self._uploaded:
+            if capturing:
+                raise RuntimeError("GradAccumulator.add(): an accumulation or gradient address changed and the table cannot be "
+                                   "uploaded during stream capture")
+            if self._entries_captured:
+                self._keep.append(self._entries)  # a graph replays from it
+                self._entries, self._entries_captured = torch.empty_like(self._entries), False
+            self._entries.copy_(self._host_table())
+            self._uploaded = self._key()
+        if capturing:
+            self._entries_captured = True
+        rc = self._lib.cabinet_grad_accum(self._entries.data_ptr(), len(self._acc), self._chunks.data_ptr(), len(self._chunks_host),
+                                          self._state.data_ptr(), self._state.numel(), int(self.max_grid), self._stream())
+        _lib.check(rc, "cabinet_grad_accum")
+
+    @torch.no_grad()
+    def reset(self):
+        """Start a new window: the next ``add()`` copies."""
+        if not self._on_device:
+            self._micro[0] = 0
+            return
+        rc = self._lib.cabinet_grad_accum_reset(self._state.data_ptr(), self._state.numel(), self._stream())
+        _lib.check(rc, "cabinet_grad_accum_reset")

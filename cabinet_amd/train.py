@@ -197,8 +197,11 @@ class _OptimizerSegment:
     declares ``capturable = True`` (``cabinet_amd.optim.FusedSGDTail``: schedule, step counter, clipping and EMA on the device)
     is recorded as it is, after its ``prepare_capture()`` has brought its address table up to date outside the capture."""
 
-    def __init__(self, optimizer, capture=False, before=None):
+    def __init__(self, optimizer, capture=False, before=None, after=None):
         self.optimizer, self.capture, self.before = optimizer, bool(capture), before
+        # after: runs behind every step() -- the accumulator's reset of a step with accum_steps > 1, recorded into the same graph
+        # as a captured step (a capturable call itself); without an optimizer it is all the segment does
+        self.after = after
         self.graph = self.snapshot = None
         if self.capture and optimizer is not None and not isinstance(optimizer, torch.optim.Optimizer) \
                 and getattr(optimizer, "capturable", None) is not True:
@@ -218,14 +221,20 @@ class _OptimizerSegment:
         self.graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(self.graph, pool=pool, capture_error_mode=_CAPTURE_MODE):
             self.optimizer.step()
+            if self.after is not None:
+                self.after()
 
     def run(self):
         if self.optimizer is None:
+            if self.after is not None:
+                self.after()
             return
         if self.graph is None:
             if self.before is not None:
                 self.before()
             self.optimizer.step()
+            if self.after is not None:
+                self.after()
             return
         if _hyper_snapshot(self.optimizer) != self.snapshot:
             raise RuntimeError("optimizer hyper-parameters changed after the optimizer step was captured in a hipGraph "
@@ -270,13 +279,31 @@ class GraphedTrainStep:
     by the optimizer segment as above.  There is no BatchNorm snapshot, no host read and no eager fallback: ``fallbacks`` stays
     0 whatever the labels, an all-ignored batch replays like any other (NaN loss, gradients exactly 0, as the eager step), and
     ``last_stats`` is the static (2,3) float64 device tensor ``[n_valid, D, S]`` per head of the last replay (``n_valid < 0``:
-    a label out of range).  ``g_bwd`` stays None; ``device_select`` is refused (there is no branch to select)."""
+    a label out of range).  ``g_bwd`` stays None; ``device_select`` is refused (there is no branch to select).
+
+    ``accum_steps = k > 1`` is the reference's accumulation contract (train.py:435-439,478-480) on the same graphs: the loss is
+    divided by ``k`` inside the captured region (the returned loss is that scaled loss, as ``TrainStep`` returns it), and behind
+    the backward of every form -- graph B, graph B-any (behind its multi-tensor copy), the focal one-graph form -- ONE
+    ``GradAccumulator.add()`` is recorded (``cabinet_grad_accum``: a captured backward overwrites its static gradient tensors on
+    every replay, so the window's sum lives in accumulation tensors of its own, allocated once at capture).  Whether a replay
+    copies or adds is read from a device counter, so the same node serves every micro-step.  ``p.grad`` is the accumulation
+    tensor at return from every call (the running sum of the window, what the reference's ``.grad`` holds); ``s_grads`` keeps the
+    per-micro-step tensors.  The optimizer segment -- captured, eager, or with a ``before_optimizer`` callback -- runs only on the
+    call that closes a window and from ``flush()`` (trailing partial window), followed by the accumulator's reset, which a captured
+    segment records in its own graph; ``optimizer=None`` closes windows by count.  The warm-up calls go through
+    ``TrainStep(accum_steps=k)`` and the graphs are recorded after the first call at or beyond ``warmup`` that closes a window, so
+    no window is split between the two paths.  An eager fallback inside a window runs forward and backward of ``loss / k`` into
+    fresh gradients, copies them into the static tensors and launches the same ``add()``.  ``accum_steps=1`` is the object
+    described above: ``accum`` is None, no launch is added, ``flush()`` does nothing."""
 
     def __init__(self, net, criteria, optimizer=None, warmup=2, capture_optimizer=False, before_optimizer=None,
-                 device_select=False):
+                 device_select=False, accum_steps=1):
         self.net, (self.crit_p, self.crit_16) = net, criteria
         self.optimizer, self.warmup = optimizer, warmup
         self.device_select = bool(device_select)
+        self.accum_steps = max(1, int(accum_steps))
+        self.accum = None  # accum_steps > 1: the GradAccumulator, built at capture
+        self._micro = 0    # graphed micro-steps taken inside the current window (the host's copy of accum.micro)
         # two focal criteria: ONE graph (forward + fused pair + loss + backward), see _capture_focal
         self.focal = isinstance(self.crit_p, SoftmaxFocalLoss) and isinstance(self.crit_16, SoftmaxFocalLoss)
         if self.focal and self.device_select:
@@ -284,10 +311,73 @@ class GraphedTrainStep:
         self.last_stats = None  # focal: the static (2,3) device tensor [n_valid, D, S] per head of the last replay
         if self.device_select:
             self.crit_p.device_select = self.crit_16.device_select = True  # the warm-up and all-ignored steps run eagerly
-        self.opt_seg = _OptimizerSegment(optimizer, capture_optimizer, before_optimizer)
-        self.eager = TrainStep(net, criteria, optimizer=optimizer, before_optimizer=before_optimizer)
+        self.opt_seg = _OptimizerSegment(optimizer, capture_optimizer, before_optimizer,
+                                         after=self._reset_accum if self.accum_steps > 1 else None)
+        self.eager = TrainStep(net, criteria, optimizer=optimizer, before_optimizer=before_optimizer,
+                               accum_steps=self.accum_steps)
         self.g_fwd = self.g_bwd = self.g_any = None
         self.fallbacks = self.device_selected = self._calls = 0  # eager fallbacks / replays of graph B-any
+
+    # ---- accum_steps > 1 ----------------------------------------------------------------------------------------------------------
+    def _reset_accum(self):
+        self.accum.reset()
+
+    def _open_accum(self, eager_grads):
+        """Before the capture: the accumulation tensors (``empty_like`` of each gradient the eager step left, whose shape and
+        strides are those of the static gradient the captured backward is about to create) and an accumulator whose gradient
+        side is still open -- the static tensors exist only once the backward has been recorded."""
+        from .optim import GradAccumulator
+
+        self._acc_params = [p for p in self.net.parameters() if p in eager_grads]
+        self.accum = GradAccumulator([(torch.empty_like(eager_grads[p], memory_format=torch.preserve_format), None)
+                                      for p in self._acc_params])
+        # the kernels' first launch must not be the recorded one: the runtime loads a code object at the first launch of one of
+        # its kernels (FusedSGDTail's have run in the eager warm-up steps, these have not); the counter is 0 already
+        self.accum.reset()
+
+    def _bind_accum(self):
+        """After the capture of the first backward: name the static gradient tensors to the accumulator."""
+        got = [p for p, _ in self.s_grads]
+        if len(got) != len(self._acc_params) or any(a is not b for a, b in zip(got, self._acc_params)):
+            raise RuntimeError(f"GraphedTrainStep(accum_steps={self.accum_steps}): the captured backward left gradients on "
+                               f"{len(got)} parameters, the eager step before it on {len(self._acc_params)}")
+        self.accum.bind([g for _, g in self.s_grads])
+        self.s_acc = [(p, a) for p, (a, _) in zip(got, self.accum.pairs)]
+        for p, a in self.s_acc:  # what the optimizer segment's capture and every caller read
+            p.grad = a
+
+    def _scaled(self, loss):
+        return loss / self.accum_steps if self.accum_steps > 1 else loss
+
+    def _finish_micro(self):
+        """Behind a micro-step whose gradients have been folded in: step if it closes the window."""
+        if self.accum_steps == 1:
+            self.opt_seg.run()
+            return
+        self._micro += 1
+        if self._micro == self.accum_steps:
+            self.opt_seg.run()  # ends with the accumulator's reset
+            self._micro = 0
+
+    def flush(self):
+        """Trailing partial accumulation window at the end of an epoch (train.py:478-480); nothing to do at accum_steps=1."""
+        if self.g_fwd is None:
+            self.eager.flush()
+        elif self._micro:
+            self.opt_seg.run()
+            self._micro = 0
+
+    def _seed_static(self, eager_grads):
+        """After the capture: nothing recorded has executed, so the tensors a caller may read get the eager step's gradients."""
+        with torch.no_grad():
+            for p, g in (self.s_acc if self.accum is not None else self.s_grads):
+                if p in eager_grads:
+                    g.copy_(eager_grads[p])
+                else:
+                    g.zero_()
+            if self.accum is not None:
+                for _, g in self.s_grads:
+                    g.zero_()
 
     def _capture_focal(self, im, lb):
         """Focal criteria have no data-dependent branch: forward, the fused pair, the loss and the backward are ONE graph.
@@ -299,21 +389,23 @@ class GraphedTrainStep:
             p.grad = None
         size = tuple(im.shape[2:])
         self.last_stats = torch.zeros((2, 3), dtype=torch.float64, device=im.device)
+        if self.accum_steps > 1:
+            self._open_accum(eager_grads)
         torch.cuda.synchronize()
         self.g_fwd = torch.cuda.CUDAGraph()
         with torch.cuda.graph(self.g_fwd, capture_error_mode=_CAPTURE_MODE):
             low, low16 = self.net.forward_lowres(self.s_im)
-            loss = focal_upsampled_pair(self.crit_p, low, self.crit_16, low16, self.s_lb, size, stats_out=self.last_stats)
+            loss = self._scaled(focal_upsampled_pair(self.crit_p, low, self.crit_16, low16, self.s_lb, size,
+                                                     stats_out=self.last_stats))
             loss.backward()
             self.s_loss = loss.detach()
+            if self.accum is not None:
+                self.accum.add()  # still ONE graph per micro-step
         self.s_grads = [(p, p.grad) for p in self.net.parameters() if p.grad is not None]
+        if self.accum is not None:
+            self._bind_accum()
         self.opt_seg.record(self.g_fwd.pool())
-        with torch.no_grad():
-            for p, g in self.s_grads:
-                if p in eager_grads:
-                    g.copy_(eager_grads[p])
-                else:
-                    g.zero_()
+        self._seed_static(eager_grads)
         torch.cuda.synchronize()
 
     def _capture(self, im, lb):
@@ -329,6 +421,8 @@ class GraphedTrainStep:
         for p in self.net.parameters():
             p.grad = None
         size = tuple(im.shape[2:])
+        if self.accum_steps > 1:
+            self._open_accum(eager_grads)
         torch.cuda.synchronize()
         self.g_fwd = torch.cuda.CUDAGraph()
         with torch.cuda.graph(self.g_fwd, capture_error_mode=_CAPTURE_MODE):
@@ -350,17 +444,16 @@ class GraphedTrainStep:
                                    "capture on a representative batch (or build the step with device_select=True)")
             self.g_bwd = torch.cuda.CUDAGraph()
             with torch.cuda.graph(self.g_bwd, pool=self.g_fwd.pool(), capture_error_mode=_CAPTURE_MODE):
-                loss = fused_pair_finish(self.prep, host)
+                loss = self._scaled(fused_pair_finish(self.prep, host))
                 loss.backward()
                 self.s_loss = loss.detach()
+                if self.accum is not None:
+                    self.accum.add()
             self.s_grads = [(p, p.grad) for p in self.net.parameters() if p.grad is not None]
+            if self.accum is not None:
+                self._bind_accum()
         self.opt_seg.record(self.g_fwd.pool())
-        with torch.no_grad():
-            for p, g in self.s_grads:
-                if p in eager_grads:
-                    g.copy_(eager_grads[p])
-                else:
-                    g.zero_()
+        self._seed_static(eager_grads)
         torch.cuda.synchronize()
 
     def _capture_both_branches(self):
@@ -373,15 +466,19 @@ class GraphedTrainStep:
         pool = self.g_fwd.pool()
         self.g_bwd = torch.cuda.CUDAGraph()
         with torch.cuda.graph(self.g_bwd, pool=pool, capture_error_mode=_CAPTURE_MODE):
-            loss = fused_pair_finish(self.prep, branch="selected")
+            loss = self._scaled(fused_pair_finish(self.prep, branch="selected"))
             loss.backward(retain_graph=True)
             self.s_loss = loss.detach()
+            if self.accum is not None:
+                self.accum.add()
         self.s_grads = [(p, p.grad) for p in self.net.parameters() if p.grad is not None]
+        if self.accum is not None:
+            self._bind_accum()
         for p, _ in self.s_grads:
             p.grad = None
         self.g_any = torch.cuda.CUDAGraph()
         with torch.cuda.graph(self.g_any, pool=pool, capture_error_mode=_CAPTURE_MODE):
-            loss = fused_pair_finish(self.prep, branch="device")
+            loss = self._scaled(fused_pair_finish(self.prep, branch="device"))
             loss.backward()
             self.s_loss_any = loss.detach()
             dst, src = [], []
@@ -393,7 +490,9 @@ class GraphedTrainStep:
                     src.append(p.grad)
             if dst:
                 torch._foreach_copy_(dst, src)
-        for p, g in self.s_grads:
+            if self.accum is not None:
+                self.accum.add()  # from graph B's static tensors: one table serves both graphs
+        for p, g in (self.s_acc if self.accum is not None else self.s_grads):
             p.grad = g
 
     @staticmethod
@@ -410,38 +509,43 @@ class GraphedTrainStep:
             # a captured first step would re-create them on every replay); the graphs are recorded after the last of them
             self._calls += 1
             loss = self.eager(im, lb)
-            if self._calls >= max(1, self.warmup):
+            # accum_steps > 1: only behind a call that closed a window, so that no window is split between the two paths
+            if self._calls >= max(1, self.warmup) and self.eager._micro == 0:
                 self._capture(im, lb)
             return loss
         _check_static_shapes(self, im, lb)
         self.s_im.copy_(im, non_blocking=True)
         self.s_lb.copy_(lb, non_blocking=True)
+        # what .grad names at return: the window's running sum at accum_steps > 1, else the graphs' own gradient tensors
+        bound = self.s_acc if self.accum is not None else self.s_grads
         if self.focal:  # one graph, nothing read on the host
-            for p, g in self.s_grads:
+            for p, g in bound:
                 p.grad = g
             self.g_fwd.replay()
-            self.opt_seg.run()
+            self._finish_micro()
             return self.s_loss
         self.snap.save()
         self.g_fwd.replay()
         host = self.s_stats.tolist()  # the step's one host sync
         if all(self._selected_branch(c, h) for c, h in zip((self.crit_p, self.crit_16), host)):
-            for p, g in self.s_grads:  # a caller's zero_grad(set_to_none=True) must not detach the graphs' gradient tensors
+            for p, g in bound:  # a caller's zero_grad(set_to_none=True) must not detach the graphs' gradient tensors
                 p.grad = g
             self.g_bwd.replay()
-            self.opt_seg.run()
+            self._finish_micro()
             return self.s_loss
         if self.g_any is not None and all(int(h[0]) > 0 for h in host):  # a head on the top-n_min branch: graph B-any
             self.device_selected += 1
-            for p, g in self.s_grads:
+            for p, g in bound:
                 p.grad = g
             self.g_any.replay()
-            self.opt_seg.run()
+            self._finish_micro()
             return self.s_loss_any
         # a head on the top-n_min branch without device_select (late training: fewer than n_min hard pixels), or a batch
         # without a valid pixel: undo graph A's BatchNorm side effects, run eagerly
         self.fallbacks += 1
         self.snap.restore()
+        if self.accum is not None:
+            return self._fallback_micro(im, lb)
         loss = self.eager(im, lb)
         for p, g in self.s_grads:  # keep the static gradient tensors the graphs write to; a step without gradient = zeros
             if p.grad is None:
@@ -450,6 +554,26 @@ class GraphedTrainStep:
                 g.copy_(p.grad)
             p.grad = g
         return loss
+
+    def _fallback_micro(self, im, lb):
+        """The eager fallback inside an accumulation window: forward and backward of ``loss / accum_steps`` into FRESH gradients
+        (the eager TrainStep would add into the window's sum and step on its own count), copied into the static gradient
+        tensors, zeros where none came, then the same accumulate launch and window logic as behind a replay."""
+        for p in self.net.parameters():
+            p.grad = None
+        low, low16 = self.net.forward_lowres(im)
+        loss = self._scaled(upsampled_pair(self.crit_p, low, self.crit_16, low16, lb, im.shape[2:]))
+        loss.backward()
+        with torch.no_grad():
+            for (p, g), (_, a) in zip(self.s_grads, self.s_acc):
+                if p.grad is None:
+                    g.zero_()
+                else:
+                    g.copy_(p.grad)
+                p.grad = a
+        self.accum.add()
+        self._finish_micro()
+        return loss.detach()
 
 
 # ---- which replay schedule GraphedDDPStep takes (round 6, VERDICT r05 item 6) -----------------------------------------------------

@@ -799,6 +799,56 @@ int cabinet_sgd_tail_step(const cabinet_sgd_tail_entry* entries, int n_entries, 
                           void* workspace, size_t workspace_bytes, cabinet_stream_t stream);
 
 /* ------------------------------------------------------------------------- *
+ * Gradient accumulation across hipGraph replays (K21; ADDITIVE to ABI version 8: no
+ * existing entry point, constant or layout changes).  Replaces what autograd's own
+ * accumulation into .grad does over a window of src/scripts/train.py:435-439 when the
+ * backward is a captured graph, which OVERWRITES its static gradient tensors on every
+ * replay.  Two launches on `stream`; nothing is allocated, synchronised or read on the
+ * host, so ONE recorded call serves every micro-step of every window.
+ *
+ * Tables (device memory, built by the caller once), K16's conventions:
+ *   entries[n_entries]  (acc, grad, numel): dense fp32 arrays of `numel` elements in the
+ *                       SAME element order; acc and grad must not overlap.
+ *   chunks[n_chunks]    cabinet_sgd_tail_chunk: length <= CABINET_SGD_TAIL_CHUNK, start a
+ *                       multiple of it, every element of every entry in exactly one chunk.
+ *                       A chunk that leaves its tensor or names no entry is ignored.
+ * Pointers need 4-byte alignment only: a chunk whose two pointers are 16-byte aligned
+ * moves as float4, the others (and each chunk's last numel % 4 elements) as scalars.
+ *
+ * State block, cabinet_grad_accum_state_bytes() (= 64) bytes of device memory, 8-byte
+ * aligned, zeroed by the caller before the first call (byte offsets; the caller may read
+ * or preset the field between calls):
+ *     0 int32 micro     micro-steps folded into acc in the current window
+ *     4 .. 63           reserved, left alone
+ *
+ * cabinet_grad_accum, per element i of every entry:
+ *     micro == 0:  acc[i] = grad[i]           a copy; acc is NOT read, so a stale NaN or
+ *                                             inf does not survive and -0.0 stays -0.0
+ *     otherwise:   acc[i] = acc[i] + grad[i]  ONE fp32 add: no scale factor (1/accum_steps
+ *                                             lives in the loss), no FMA -- the bits of
+ *                                             autograd's accumulation in the same order
+ *   then, in a one-lane launch BEHIND the pass, micro += 1 (a plain store): every
+ *   workgroup of the pass reads the same micro.  No atomics, no scratch, no reduction:
+ *   the result does not depend on the grid and is bit-reproducible.  Nothing outside
+ *   [acc, acc + numel) is written.
+ * cabinet_grad_accum_reset: micro = 0 (one-lane launch): the next call starts a window.
+ * max_grid: 0 = the default cap of 2048 workgroups; smaller values force the
+ * grid-stride loop (tests).
+ * Errors: -1 for a null table or state block, a non-positive count, a negative max_grid
+ * or a misaligned table; -3 for state_bytes < cabinet_grad_accum_state_bytes().
+ * ------------------------------------------------------------------------- */
+typedef struct cabinet_grad_accum_entry {
+    float* acc;
+    const float* grad;
+    long long numel;
+} cabinet_grad_accum_entry; /* 24 bytes */
+
+size_t cabinet_grad_accum_state_bytes(void);
+int cabinet_grad_accum(const cabinet_grad_accum_entry* entries, int n_entries, const cabinet_sgd_tail_chunk* chunks, int n_chunks,
+                       void* state, size_t state_bytes, int max_grid, cabinet_stream_t stream);
+int cabinet_grad_accum_reset(void* state, size_t state_bytes, cabinet_stream_t stream);
+
+/* ------------------------------------------------------------------------- *
  * Training augmentation (K18; ADDITIVE to ABI version 8: no existing entry point, constant or layout changes).
  * Replaces, for a batch, what src/datasets/cityscapes.py does to a decoded train sample: :114-136 (RandomHorizontalFlip,
  * RandomScale, RandomCrop with reflect padding, RandomColorJitter, RandomGrayscale, RandomGamma, RandomNoise, RandomCutout of
