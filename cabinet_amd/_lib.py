@@ -104,6 +104,8 @@ SIGNATURES = {
     "cabinet_conv3x3s2_wgrad_workspace_bytes": (_SZ, [_INT] * 5),
     "cabinet_conv3x3s2_wgrad": (_INT, [_PTR] * 2 + [_INT] * 5 + [_PTR] + [_PTR, _SZ, _PTR]),
     "cabinet_conv3x3s2_dgrad": (_INT, [_PTR] * 2 + [_INT] * 5 + [_PTR] + [_PTR]),
+    "cabinet_conv3x3s2_fwd_supported": (_INT, [_INT] * 2),
+    "cabinet_conv3x3s2_fwd": (_INT, [_PTR] * 2 + [_INT] * 5 + [_PTR] + [_PTR]),
     "cabinet_bn_act_fwd_part": (_INT, [_PTR] * 7 + [_INT] * 6 + [_FLT, _FLT] + [_PTR] * 3 + [_PTR]),
     "cabinet_conv3x3_supported": (_INT, [_INT] * 3),
     "cabinet_conv3x3_tile_blocks": (_INT, [_INT] * 3),

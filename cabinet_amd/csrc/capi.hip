@@ -137,6 +137,9 @@ hipError_t conv3x3s2_wgrad_run(const float* dy, const float* x, int B, int Ci, i
                                hipStream_t stream);
 long long conv3x3s2_dgrad_workgroups(int B, int H, int W);
 hipError_t conv3x3s2_dgrad_run(const float* dy, const float* w, int B, int H, int W, float* dx, hipStream_t stream);
+bool conv3x3s2_fwd_supported(int Ci, int Co);
+long long conv3x3s2_fwd_workgroups(int B, int H, int W);
+hipError_t conv3x3s2_fwd_run(const float* x, const float* w, int B, int H, int W, float* y, hipStream_t stream);
 // pwconv.hip
 bool pwconv_supported(int Ci, int Co, int P);
 size_t pwconv_bwd_workspace(int B, int Ci, int Co, int P);
@@ -1351,7 +1354,7 @@ int cabinet_pwconv_wide_wgrad(const float* dy, const float* x, int B, int Ci, in
                       "pwconv_wide_wgrad launch");
 }
 
-// ------------------------------------------------------ 3x3 stride-2 convolution: weight and input gradient
+// ------------------------------------------------------ 3x3 stride-2 convolution: weight and input gradient, 64 -> 64 forward
 static bool conv3x3s2_size_ok(int B, int Ci, int H, int W) {  // the kernels index with 64 bits; the grid is one workgroup per slab
     return cabinet::conv3x3s2_wgrad_slabs(B, Ci, H, W) <= (1ll << 30);
 }
@@ -1391,6 +1394,19 @@ int cabinet_conv3x3s2_dgrad(const float* dy, const float* w, int B, int Ci, int 
     if ((reinterpret_cast<size_t>(dx) & 7) != 0)
         return fail(CABINET_ERR_INVALID_ARG, "conv3x3s2_dgrad: dx must be 8-byte aligned");
     return hip_status(cabinet::conv3x3s2_dgrad_run(dy, w, B, H, W, dx, static_cast<hipStream_t>(stream)), "conv3x3s2_dgrad launch");
+}
+
+int cabinet_conv3x3s2_fwd_supported(int Ci, int Co) { return cabinet::conv3x3s2_fwd_supported(Ci, Co) ? 1 : 0; }
+
+int cabinet_conv3x3s2_fwd(const float* x, const float* w, int B, int Ci, int Co, int H, int W, float* y, cabinet_stream_t stream) {
+    if (B <= 0 || Ci <= 0 || Co <= 0 || H <= 0 || W <= 0)
+        return fail(CABINET_ERR_INVALID_ARG, "conv3x3s2_fwd: non-positive dimension");
+    if (!cabinet::conv3x3s2_fwd_supported(Ci, Co))
+        return fail(CABINET_ERR_UNSUPPORTED, "conv3x3s2_fwd: Ci=%d, Co=%d ((64, 64) is compiled)", Ci, Co);
+    if (cabinet::conv3x3s2_fwd_workgroups(B, H, W) > (1ll << 30))
+        return fail(CABINET_ERR_UNSUPPORTED, "conv3x3s2_fwd: B=%d, H=%d, W=%d: grid too large", B, H, W);
+    if (!x || !w || !y) return fail(CABINET_ERR_INVALID_ARG, "conv3x3s2_fwd: null tensor pointer");
+    return hip_status(cabinet::conv3x3s2_fwd_run(x, w, B, H, W, y, static_cast<hipStream_t>(stream)), "conv3x3s2_fwd launch");
 }
 
 // ------------------------------------------------------ dense 3x3 convolution (Winograd F(2x2,3x3), fp32 MFMA)

@@ -1,11 +1,12 @@
-// K15 -- weight gradient (and, 64 -> 64, input gradient) of the 3x3 stride-2 padding-1 bias-free convolutions, NCHW fp32, no
-// layout copy.
+// K15 -- weight gradient (and, 64 -> 64, input gradient and forward) of the 3x3 stride-2 padding-1 bias-free convolutions, NCHW
+// fp32, no layout copy.
 //
 // Serves the spatial branch's conv2 / conv3 (64 -> 64, reference src/models/cabinet.py:112-113, SpatialBranch) and the
 // backbone's first layer (3 -> 16, reference src/models/mobilenetv3.py:86-91,173, conv_3x3_bn(3, 16, 2)).  MIOpen computes these
 // weight gradients with NHWC implicit-GEMM kernels and first copies x and dy to NHWC and dw back; the product
 //     dW[co][ci][ky][kx] = sum_{b,oy,ox} dY[b][co][oy][ox] * X[b][ci][2 oy - 1 + ky][2 ox - 1 + kx]
-// contracts over pixels, the contiguous axis of BOTH operands in NCHW.  The forward stays the stock operator's.
+// contracts over pixels, the contiguous axis of BOTH operands in NCHW.  The 3 -> 16 forward stays the stock operator's (NCHW
+// there, no copies); the 64 -> 64 forward is the last section below.
 //
 //   64 -> 64 : a workgroup (4 waves) walks output rows oy of one 32-pixel column tile.  Per row it multiplies the 64 x 32 dy
 //              segment ([co][33]) and the 64 x 3 x 65 input patch ([ci][3 slots][65]: channel pitch 195, odd, so the 32
@@ -42,6 +43,36 @@
 // B operands (16); no scratch.  The staging this replaces (both rows of a pair between two barriers, ~33 loads per thread each
 // behind two divisions and a bounds select, row m + 1 fetched twice) ran at 0.41 of the fp32 MFMA rate with 0.46 of the wave
 // cycles parked; this one at 0.73 with 0.11.
+//
+// Forward, 64 -> 64 (conv3x3s2_fwd64_kernel):
+//     Y[b][co][oy][ox] = sum_{ci,ky,kx} W[co][ci][ky][kx] * X[b][ci][2 oy - 1 + ky][2 ox - 1 + kx]
+// the gather form of the input gradient's scatter (the stock operator runs it as an NHWC implicit GEMM between a copy of x to
+// NHWC and a copy of y back).  M = co, N = output pixels, K = ci x 9 taps = 576 on the exact-fp32 MFMA 16x16x4: a wave owns 16
+// output channels and keeps their 64 x 9 weights in 144 registers for the whole kernel (the A operand never touches the LDS).
+// A workgroup (4 waves) walks the output rows oy of one strip (cv_plan: 512 workgroups aimed at) of one T = 32 column tile of one
+// image.  The input lives in LDS as a ring of three rows (2 oy - 1, 2 oy, 2 oy + 1) of all 64 channels; row 2 oy + 1 stays in its
+// slot for the next step, the two new rows are requested before the step's MFMAs (33 registers per thread: whole-wave row
+// segments at wave-uniform (ci, row) bases, lane = column, unconditional clamped loads) and written behind them, 0 selected on
+// the way into LDS for iy = -1, iy >= H, ix = -1, ix >= W: nothing is masked by multiplication.  Every input row is fetched once
+// per workgroup (the first step's three rows are the only unpipelined fetch).  Two barriers per step, as in the weight gradient.
+//   B operand : tap kx of 16 neighbouring output pixels reads input columns 2 ox - 1 + kx, a stride of 2; so a row is staged split
+//               by column parity -- [patch columns 0, 2, .., 2 T | 1, 3, .., 2 T - 1] -- and every B read is a unit-stride run
+//               of 16 (kx = 0: even run at n, kx = 1: odd run at n, kx = 2: even run at n + 1).  Row pitch 66, channel pitch 208
+//               = 16 mod 32: the two k-groups (channels 4 ks + lk) of a 32-lane ds_read_b32 group fall on disjoint banks.
+//   order     : tap by tap, the 64 input channels of a tap as two interleaved chains of 32 terms, folded into the pixel's sum
+//               in tap order (the fold is pinned where it is written: sunk to the guarded store it kept nine taps' partials
+//               live and spilled 26 registers).  The order does not depend on the strip, the tile or the launch; no atomics.
+//   stores    : register r of a lane is output channel co0 + 4 lk + r of its pixel: 16 lanes store a 64-byte run of a row of y.
+//   resources : 214 VGPRs (144 weights, 4 accumulators, 8 tap partials, two half-taps of B operands, 33 prefetch), no scratch,
+//               53,248 B of LDS: two workgroups per CU.  The group loop is not unrolled and the half-taps are fenced as in the
+//               input gradient.  In the step the 33 staging loads issue before the first MFMA; the waits ahead of them only
+//               retire the previous step's stores of y, the loads are first waited for behind the last MFMA.
+//   measured  : operator alone, hipGraph replay against the whole stock call (profiles/conv3x3s2_fwd64_summary.md), share of the
+//               157.3 TFLOP/s fp32 MFMA rate: sb.conv2 / sb.conv3 at config 3 0.66 / 0.59 (373 and 104 us against 626 and 153),
+//               at config 5 0.64 / 0.50, of one 1024 x 2048 image 0.56 / 0.40; the shorter the strip, the larger the share of
+//               the unpipelined first step.  The T = 64 variant (-DCABINET_CV_TW=64: 102,400 B of LDS, one workgroup per CU,
+//               246 VGPRs, the same bits) ran at 0.50 / 0.45 / 0.47 / 0.41 / 0.45 / 0.36 of the rate: with one wave per SIMD
+//               nothing covers the barriers and the LDS writes of the hand-over.  T = 32 is what is built.
 #include "common.hpp"
 #include "slab_sum.hpp"
 
@@ -392,8 +423,198 @@ __global__ __launch_bounds__(256, 2) void conv3x3s2_dgrad64_kernel(const float* 
     }
 }
 
+// ------------------------------------------------------------------------------------------------ forward, 64 -> 64
+#ifndef CABINET_CV_TW
+#define CABINET_CV_TW 32  // 64 is the one-workgroup-per-CU variant the header's table was measured with
+#endif
+constexpr int CV_TW = CABINET_CV_TW;   // output columns of a tile: 2 T + 1 input columns
+constexpr int CV_NSEG = CV_TW / 32;    // 64-column wave segments of an input row
+constexpr int CV_EV = 0;               // run of the patch columns j = 2 n (ix = 2 (ox0 + n) - 1), n = 0 .. T: taps kx = 0 (n) and 2 (n + 1)
+constexpr int CV_OD = CV_TW + 1;       // run of the patch columns j = 2 n + 1 (ix = 2 (ox0 + n)), n = 0 .. T - 1: tap kx = 1
+constexpr int CV_RP = 2 * CV_TW + 2;   // row pitch (2 T + 1 live)
+constexpr int CV_CP = (3 * CV_RP - 16 + 31) / 32 * 32 + 16;  // channel pitch >= 3 rows, = 16 mod 32: 208 (T 32), 400 (T 64)
+constexpr int CV_PR = CW_C / 4;        // 16 channels' row segments per wave and input row
+constexpr int CV_WG_PER_CU = CV_TW == 32 ? 2 : 1;
+constexpr int CV_TARGET_WG = 256 * CV_WG_PER_CU;
+constexpr size_t CV_LDS = (size_t)CW_C * CV_CP * sizeof(float);  // 53,248 B (T 32), 102,400 B (T 64)
+static_assert(CV_TW == 32 || CV_TW == 64, "the staging covers a row with one or two 64-lane segments");
+static_assert(CV_CP % 32 == 16 && CV_CP >= 3 * CV_RP, "k-groups lk and lk + 1 of a 32-lane read group on disjoint banks");
+
+__host__ __device__ constexpr int cv_koff(int kx) { return kx == 0 ? CV_EV : kx == 1 ? CV_OD : CV_EV + 1; }
+
+__global__ __launch_bounds__(256, CV_WG_PER_CU) void conv3x3s2_fwd64_kernel(const float* __restrict__ x, const float* __restrict__ w,
+                                                                          C3Shape s, int tiles_x, int strips, int rows_per,
+                                                                          float* __restrict__ y) {
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    float* xs = smem;  // [ci][3 slots][even run | odd run]: a ring of input rows, each split by column parity
+    const int tid = threadIdx.x, wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63, lc = lane & 15, lk = lane >> 4;
+    int bi = blockIdx.x;
+    const int tx = bi % tiles_x;
+    bi /= tiles_x;
+    const int strip = bi % strips, b = bi / strips;
+    const int oy_begin = strip * rows_per, oy_end = min(s.Ho, oy_begin + rows_per);
+    const int ox0 = tx * CV_TW, ix0 = 2 * ox0 - 1;
+    const int co0 = 16 * wave;  // this wave's 16 output channels: their 64 x 9 weights stay in registers
+
+    float wr[9][16];
+#pragma unroll
+    for (int t = 0; t < 9; ++t)
+#pragma unroll
+        for (int ks = 0; ks < 16; ++ks) wr[t][ks] = w[((co0 + lc) * CW_C + 4 * ks + lk) * 9 + t];
+
+    const float* xb = x + (size_t)b * CW_C * s.H * s.W;
+    float* yb = y + ((size_t)b * CW_C + co0 + 4 * lk) * s.Ho * s.Wo;
+    const float* brow = xs + lk * CV_CP + lc;
+    // Staging.  An input row is 64 channels x (2 T + 1) columns: this wave's 16 channels as row segments (wave-uniform (ci, row)
+    // base, lane = column ix = 2 ox0 + c, c = 64 sg + lane: patch column j = c + 1, so even c goes to the odd run and odd c to
+    // the even run) and the left halo column ix0 (j = 0) as one element per thread (thread = (row of the request, channel)).
+    // Every load is unconditional: row and column are clamped into the tensor, and what lies outside it (iy = -1, iy >= H,
+    // ix = -1, ix >= W) is replaced by 0 on the way into LDS.
+    unsigned colo[CV_NSEG];
+    int dcol[CV_NSEG];
+    bool col_ok[CV_NSEG];
+#pragma unroll
+    for (int sg = 0; sg < CV_NSEG; ++sg) {
+        const int c = 64 * sg + lane;
+        colo[sg] = (unsigned)min(2 * ox0 + c, s.W - 1) * 4u;
+        col_ok[sg] = 2 * ox0 + c < s.W;
+        dcol[sg] = (c & 1) ? CV_EV + (c + 1) / 2 : CV_OD + c / 2;
+    }
+    const bool halo_ok = ix0 >= 0;
+    const int hrow = tid >> 6, hch = tid & 63;
+    float xr[2 * CV_PR * CV_NSEG], xh;
+    auto request = [&](int nr, int iya, int iyb) {  // rows iya (and, nr = 2, iyb) of x
+        const int ya = min(max(iya, 0), s.H - 1), yb_ = min(max(iyb, 0), s.H - 1);
+#pragma unroll
+        for (int j = 0; j < CV_PR; ++j)
+#pragma unroll
+            for (int sg = 0; sg < CV_NSEG; ++sg)
+                xr[j * CV_NSEG + sg] = cd_ld(xb + ((size_t)(CV_PR * wave + j) * s.H + ya) * s.W, colo[sg]);
+        if (nr == 2) {
+#pragma unroll
+            for (int j = 0; j < CV_PR; ++j)
+#pragma unroll
+                for (int sg = 0; sg < CV_NSEG; ++sg)
+                    xr[(CV_PR + j) * CV_NSEG + sg] = cd_ld(xb + ((size_t)(CV_PR * wave + j) * s.H + yb_) * s.W, colo[sg]);
+        }
+        xh = xb[((size_t)hch * s.H + (hrow == 0 ? ya : yb_)) * s.W + max(ix0, 0)];
+    };
+    auto commit = [&](int nr, int iya, int iyb, int sa, int sb) {
+        const bool oka = iya >= 0 && iya < s.H, okb = iyb >= 0 && iyb < s.H;
+        float* d = xs + CV_PR * wave * CV_CP;
+#pragma unroll
+        for (int j = 0; j < CV_PR; ++j)
+#pragma unroll
+            for (int sg = 0; sg < CV_NSEG; ++sg)
+                d[j * CV_CP + sa * CV_RP + dcol[sg]] = (oka && col_ok[sg]) ? xr[j * CV_NSEG + sg] : 0.f;
+        if (nr == 2) {
+#pragma unroll
+            for (int j = 0; j < CV_PR; ++j)
+#pragma unroll
+                for (int sg = 0; sg < CV_NSEG; ++sg)
+                    d[j * CV_CP + sb * CV_RP + dcol[sg]] = (okb && col_ok[sg]) ? xr[(CV_PR + j) * CV_NSEG + sg] : 0.f;
+        }
+        if (hrow < nr) xs[hch * CV_CP + (hrow == 0 ? sa : sb) * CV_RP + CV_EV] = ((hrow == 0 ? oka : okb) && halo_ok) ? xh : 0.f;
+    };
+    // Input row iy of the strip lives in slot (iy - iy_begin) % 3.  Step oy multiplies rows 2 oy - 1 .. 2 oy + 1 (slots s0, s1, s2)
+    // while the two new rows of step oy + 1 are in flight in registers; behind the MFMAs they are written over rows 2 oy - 1
+    // and 2 oy, and row 2 oy + 1 stays where it is: every input row is fetched once per workgroup.
+    const int iy_begin = 2 * oy_begin - 1;
+    request(2, iy_begin, iy_begin + 1);
+    commit(2, iy_begin, iy_begin + 1, 0, 1);
+    request(1, iy_begin + 2, iy_begin + 2);
+    commit(1, iy_begin + 2, iy_begin + 2, 2, 2);
+    __syncthreads();
+    int s0 = 0;  // slot of row 2 oy - 1
+    for (int oy = oy_begin; oy < oy_end; ++oy) {
+        const int s1 = s0 == 2 ? 0 : s0 + 1, s2 = s1 == 2 ? 0 : s1 + 1;
+        const bool more = oy + 1 < oy_end;
+        if (more) request(2, 2 * oy + 2, 2 * oy + 3);  // in flight underneath this step's MFMAs
+        const float* bp0 = brow + s0 * CV_RP;  // row 2 oy - 1
+        const float* bp1 = brow + s1 * CV_RP;  // row 2 oy
+        const float* bp2 = brow + s2 * CV_RP;  // row 2 oy + 1
+#pragma unroll 1  // 144 MFMAs per group already: unrolling the groups only spills the weights
+        for (int ng = 0; ng < CV_TW / 16 && ox0 + 16 * ng < s.Wo; ++ng) {
+            f32x4v acc = f32x4v{0.f, 0.f, 0.f, 0.f};
+            // tap by tap, the 64 input channels of a tap as two interleaved chains of 32 (k-steps of 4 channels, even and odd: no
+            // MFMA waits on the one before it), folded into the pixel's sum in tap order: the longest fp32 chain is 32 terms, and
+            // the order does not depend on where the pixel sits.  The B operands of half-tap g + 1 (8 k-steps) are read while
+            // half-tap g is multiplied, and no further ahead (the scheduling barrier), as in the input gradient.
+            float bv[2][8];
+            auto read_half = [&](int g, float* v) {
+                const int t = g / 2, ky = t / 3;
+                const float* bt = (ky == 0 ? bp0 : ky == 1 ? bp1 : bp2) + 16 * ng + cv_koff(t % 3);
+#pragma unroll
+                for (int i = 0; i < 8; ++i) v[i] = bt[4 * (8 * (g % 2) + i) * CV_CP];
+            };
+            read_half(0, bv[0]);
+            f32x4v p0, p1;
+#pragma unroll
+            for (int g = 0; g < 18; ++g) {
+                const int t = g / 2, k8 = 8 * (g % 2);
+                if (g + 1 < 18) read_half(g + 1, bv[(g + 1) & 1]);
+                if (g % 2 == 0) p0 = p1 = f32x4v{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+                for (int i = 0; i < 8; i += 2) {
+                    p0 = mfma16(wr[t][k8 + i], bv[g & 1][i], p0);
+                    p1 = mfma16(wr[t][k8 + i + 1], bv[g & 1][i + 1], p1);
+                }
+                if (g % 2 == 1) {
+                    acc += p0 + p1;
+                    asm volatile("" : "+v"(acc));  // folded here: sunk to the guarded store, nine taps' partials would stay live
+                }
+                __builtin_amdgcn_sched_barrier(0);
+            }
+            // register r is output channel co0 + 4 lk + r of pixel ox: 16 lanes store 64 contiguous bytes of a row of y
+            const int ox = ox0 + 16 * ng + lc;
+            if (ox < s.Wo) {
+#pragma unroll
+                for (int r = 0; r < 4; ++r) yb[((size_t)r * s.Ho + oy) * s.Wo + ox] = acc[r];
+            }
+        }
+        if (more) {
+            __syncthreads();  // every wave has read this step's operands
+            commit(2, 2 * oy + 2, 2 * oy + 3, s0, s1);
+            __syncthreads();
+        }
+        s0 = s2;
+    }
+}
+
 // ------------------------------------------------------------------------------------------------ host side
 bool conv3x3s2_supported(int Ci, int Co) { return (Ci == CW_C && Co == CW_C) || (Ci == CF_CI && Co == CF_CO); }
+bool conv3x3s2_fwd_supported(int Ci, int Co) { return Ci == CW_C && Co == CW_C; }
+
+static C3Plan cv_plan(const C3Shape& s) {  // strips of output rows per (image, column tile), as cd_plan
+    C3Plan p;
+    p.tiles_x = ceil_div(s.Wo, CV_TW);
+    const long per = (long)s.B * p.tiles_x;
+    long strips = CV_TARGET_WG / per;
+    if (strips > s.Ho) strips = s.Ho;
+    if (strips < 1) strips = 1;
+    p.rows_per = ceil_div(s.Ho, (int)strips);
+    p.strips = ceil_div(s.Ho, p.rows_per);
+    return p;
+}
+
+long long conv3x3s2_fwd_workgroups(int B, int H, int W) {
+    const C3Shape s = c3_shape(B, H, W);
+    const long long per = (long long)B * ceil_div(s.Wo, CV_TW);
+    if (per > (1ll << 30)) return per;
+    const C3Plan p = cv_plan(s);
+    return per * p.strips;
+}
+
+hipError_t conv3x3s2_fwd_run(const float* x, const float* w, int B, int H, int W, float* y, hipStream_t stream) {
+    const C3Shape s = c3_shape(B, H, W);
+    const C3Plan p = cv_plan(s);
+    static lds_attr_mask mask{0};
+    if (hipError_t e = ensure_dynamic_lds(reinterpret_cast<const void*>(conv3x3s2_fwd64_kernel), CV_LDS, mask); e != hipSuccess)
+        return e;
+    hipLaunchKernelGGL(conv3x3s2_fwd64_kernel, dim3(B * p.tiles_x * p.strips), dim3(256), CV_LDS, stream, x, w, s, p.tiles_x,
+                       p.strips, p.rows_per, y);
+    return hipGetLastError();
+}
 
 static C3Plan cd_plan(const C3Shape& s) {  // strips of row pairs m per (image, 64-column tile), as cw_plan
     C3Plan p;

@@ -1884,9 +1884,9 @@ CONV3X3S2_ENABLED = _os.environ.get("CABINET_CONV3X3S2", "1") != "0"
 def conv3x3s2_supported(conv, x):
     """True for the bias-free 3x3 stride-2 padding-1 convolutions whose BACKWARD K15 computes straight on NCHW (the spatial
     branch's conv2 / conv3, reference cabinet.py:112-113, and the backbone's first layer, mobilenetv3.py:173) -- in a forward
-    that records a graph for autograd only; fp32 device tensors outside autocast.  The forward stays the stock operator's; which
-    gradient of which layer goes native is _Conv3x3S2's business (64 -> 64: dx always, dw by _conv3x3s2_native_wgrad64; 3 -> 16: dw
-    by _conv3x3s2_native_wgrad)."""
+    that records a graph for autograd only; fp32 device tensors outside autocast.  Which part of which layer goes native is
+    _Conv3x3S2's business (64 -> 64: the forward by _conv3x3s2_native_fwd64, dx always, dw by _conv3x3s2_native_wgrad64;
+    3 -> 16: stock forward, dw by _conv3x3s2_native_wgrad)."""
     if not (CONV3X3S2_ENABLED and isinstance(conv, torch.nn.Conv2d) and x.is_cuda and x.dim() == 4):
         return False
     if not (conv.kernel_size == (3, 3) and conv.stride == (2, 2) and conv.padding == (1, 1) and conv.groups == 1
@@ -1934,15 +1934,83 @@ def _conv3x3s2_native_wgrad64(B, H, W):
     return workgroups >= _CW_MIN_WORKGROUPS and rows_per >= _CW_MIN_ROWS
 
 
+# CABINET_CONV3X3S2_FWD64=0: the 64 -> 64 forward alone goes back to the stock operator (MIOpen's NHWC implicit GEMM with its
+# NCHW <-> NHWC copies) -- same-box A/B timing only
+CONV3X3S2_FWD64_ENABLED = _os.environ.get("CABINET_CONV3X3S2_FWD64", "1") != "0"
+_CV_TILE = 32             # output columns of a workgroup's tile (CV_TW of csrc/conv3x3_s2.hip)
+_CV_MIN_WORKGROUPS = 256  # one per CU
+_CV_MIN_ROWS = 2          # output rows a workgroup walks: the shortest strip measured (the ring's hand-over runs at least once)
+
+
+def _conv3x3s2_fwd64_plan(B, H, W):
+    """cv_plan of csrc/conv3x3_s2.hip restated -> (workgroups, rows_per): 32-column tiles, strips of output rows, 512 workgroups
+    aimed at."""
+    Ho, Wo = (H - 1) // 2 + 1, (W - 1) // 2 + 1
+    tiles = -(-Wo // _CV_TILE)
+    strips = max(1, min(512 // (B * tiles), Ho))
+    rows_per = -(-Ho // strips)
+    return B * tiles * -(-Ho // rows_per), rows_per
+
+
+def _conv3x3s2_native_fwd64(B, H, W):
+    """The routing rule of cabinet_conv3x3s2_fwd, by measurement on MI355X (tools/time_conv3x3s2_fwd64.py,
+    profiles/conv3x3s2_fwd64_summary.md): native where the plan gives every CU a workgroup and every workgroup a strip of at
+    least two rows, which is where it was measured against the stock call with its layout copies (sb.conv2 and sb.conv3 at
+    config 3 and 5 and of one 1024 x 2048 image: 512 workgroups of 32, 8, 16, 4, 8 and 2 rows).  Planes whose workgroups get a
+    single row each were not measured and keep the stock operator."""
+    if not CONV3X3S2_FWD64_ENABLED:
+        return False
+    workgroups, rows_per = _conv3x3s2_fwd64_plan(B, H, W)
+    return workgroups >= _CV_MIN_WORKGROUPS and rows_per >= _CV_MIN_ROWS
+
+
+def conv3x3s2_fwd64(x, weight):
+    """y = conv2d(x, weight, stride 2, padding 1) of a 64 -> 64 layer by cabinet_conv3x3s2_fwd: dense fp32 NCHW device tensors,
+    no autograd, no workspace; capturable.  Whatever the routing rule says: the callers ask it."""
+    if not (x.is_cuda and x.dim() == 4 and x.dtype == torch.float32 and weight.dtype == torch.float32
+            and tuple(weight.shape) == (64, 64, 3, 3) and x.shape[1] == 64):
+        raise RuntimeError("conv3x3s2_fwd64: fp32 device tensors, x (B, 64, H, W), weight (64, 64, 3, 3)")
+    xc, wc = _f32c(x.detach()), _f32c(weight.detach())
+    B, H, W = xc.shape[0], xc.shape[2], xc.shape[3]
+    y = torch.empty((B, 64, (H - 1) // 2 + 1, (W - 1) // 2 + 1), dtype=torch.float32, device=x.device)
+    with torch.cuda.device(x.device):
+        rc = _lib.load().cabinet_conv3x3s2_fwd(_ptr(xc), _ptr(wc), B, 64, 64, H, W, _ptr(y), _stream_handle(x.device))
+    _lib.check(rc, "cabinet_conv3x3s2_fwd")
+    return y
+
+
+def _conv3x3s2_fwd64_nograd(conv, x, weight):
+    """True where Conv2dS2 takes the native forward outside autograd (evaluation, inference): a bias-free 3x3 stride-2 padding-1
+    64 -> 64 layer, dense-able fp32 device input, no graph being recorded, outside autocast, and the routing rule holds."""
+    if not (CONV3X3S2_ENABLED and x.is_cuda and x.dim() == 4 and x.shape[0] >= 1 and x.shape[2] * x.shape[3] >= 1):
+        return False
+    if not (conv.kernel_size == (3, 3) and conv.stride == (2, 2) and conv.padding == (1, 1) and conv.groups == 1
+            and conv.bias is None and conv.dilation == (1, 1) and conv.padding_mode == "zeros"
+            and conv.in_channels == 64 and conv.out_channels == 64 and x.shape[1] == 64):
+        return False
+    if torch.is_autocast_enabled() or x.dtype != torch.float32 or weight.dtype != torch.float32 or not weight.is_cuda:
+        return False
+    if torch.is_grad_enabled() and (x.requires_grad or weight.requires_grad):
+        return False
+    if not _conv3x3s2_native_fwd64(x.shape[0], x.shape[2], x.shape[3]):
+        return False
+    return bool(_lib.load().cabinet_conv3x3s2_fwd_supported(64, 64))
+
+
 class _Conv3x3S2(torch.autograd.Function):
-    """y = conv2d(x, weight, stride 2, padding 1) with the stock forward; dx of the 64 -> 64 layers by cabinet_conv3x3s2_dgrad
-    (the 3 -> 16 layer reads the image and has none), dw by cabinet_conv3x3s2_wgrad where the form's rule says so
-    (_conv3x3s2_native_wgrad64 for 64 -> 64, _conv3x3s2_native_wgrad for 3 -> 16), else by the stock operator."""
+    """y = conv2d(x, weight, stride 2, padding 1): the forward of the 64 -> 64 layers by cabinet_conv3x3s2_fwd where
+    _conv3x3s2_native_fwd64 says so, else (and for the 3 -> 16 layer always) the stock forward; dx of the 64 -> 64 layers by
+    cabinet_conv3x3s2_dgrad (the 3 -> 16 layer reads the image and has none), dw by cabinet_conv3x3s2_wgrad where the form's
+    rule says so (_conv3x3s2_native_wgrad64 for 64 -> 64, _conv3x3s2_native_wgrad for 3 -> 16), else by the stock operator.
+    What is saved and the backward do not depend on which forward ran."""
 
     @staticmethod
     def forward(fn_ctx, x, weight):
         x = x.contiguous()  # dense NCHW for the stock operator too (a no-op in the model): a channels_last input sends it to another solver
-        y = F.conv2d(x, weight, None, 2, 1)
+        if weight.shape[0] == 64 and weight.shape[1] == 64 and _conv3x3s2_native_fwd64(x.shape[0], x.shape[2], x.shape[3]):
+            y = conv3x3s2_fwd64(x, weight)
+        else:
+            y = F.conv2d(x, weight, None, 2, 1)
         fn_ctx.save_for_backward(x, weight)
         return y
 
@@ -1979,12 +2047,16 @@ class _Conv3x3S2(torch.autograd.Function):
 
 class Conv2dS2(torch.nn.Conv2d):
     """``nn.Conv2d`` (same parameters, same ``state_dict``) whose convolution is ``_Conv3x3S2`` where conv3x3s2_supported says
-    so and the stock operator everywhere else.  The route sits inside the module's own call, so forward hooks and pre-hooks
-    registered on the layer see it as they see any convolution.  The models build their stride-2 3x3 layers with it."""
+    so (a forward that records a graph), cabinet_conv3x3s2_fwd called directly where _conv3x3s2_fwd64_nograd says so (the
+    64 -> 64 layers in evaluation and inference) and the stock operator everywhere else.  The route sits inside the module's
+    own call, so forward hooks and pre-hooks registered on the layer see it as they see any convolution.  The models build
+    their stride-2 3x3 layers with it."""
 
     def _conv_forward(self, input, weight, bias):
         if bias is None and conv3x3s2_supported(self, input):
             return _Conv3x3S2.apply(input, weight)
+        if bias is None and _conv3x3s2_fwd64_nograd(self, input, weight):
+            return conv3x3s2_fwd64(input, weight)
         return super()._conv_forward(input, weight, bias)
 
 

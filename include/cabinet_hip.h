@@ -695,12 +695,17 @@ int cabinet_predict_render(const unsigned char* labels, const float* image, cons
  * ConvBNReLU(64, 64, kernel_size=3, stride=2, padding=1), src/models/cabinet.py:112-113 (SpatialBranch.conv2 / conv3,
  * forward cabinet.py:42), and of conv_3x3_bn(3, input_channel, 2), src/models/mobilenetv3.py:173 (:86-91), the backbone's
  * first layer.  Exact-fp32 MFMA with fp32 accumulation, one slab per workgroup, ordered slab sum: no atomics,
- * bit-reproducible, capturable (the workspace comes from the caller).  The forward stays with the stock operator.
+ * bit-reproducible, capturable (the workspace comes from the caller).
  * Supported (cabinet_conv3x3s2_supported): (Ci, Co) = (64, 64) or (3, 16); any B, H, W >= 1.
  *   dgrad (64 -> 64 only; the 3 -> 16 layer reads the image): w (Co,Ci,3,3),
  *     dx (B,Ci,H,W)[., iy, ix] = sum_{co,ky,kx} w[co,.,ky,kx] * dy[., co, (iy + 1 - ky) / 2, (ix + 1 - kx) / 2]
  *   over the taps with integer, in-range quotients, by the four parity classes of (iy, ix): no product with a structural
  *   zero.  Every element of dx is written; no workspace, fixed summation order.
+ *   fwd (cabinet_conv3x3s2_fwd_supported: (Ci, Co) = (64, 64) only; the 3 -> 16 layer keeps the stock forward):
+ *     y (B,Co,Ho,Wo)[., oy, ox] = sum_{ci,ky,kx} w[.,ci,ky,kx] * x (B,Ci,H,W)[., ci, 2 oy - 1 + ky, 2 ox - 1 + kx]
+ *   with zero padding, i.e. conv2d(x, w, stride 2, padding 1) of ConvBNReLU(64, 64, 3, 2, 1), cabinet.py:112-113, straight
+ *   on NCHW.  Any B, H, W >= 1, tensors at 4-byte alignment; every element of y is written; no workspace, no atomics, a
+ *   fixed summation order that does not depend on the launch plan.
  * ------------------------------------------------------------------------- */
 int cabinet_conv3x3s2_supported(int Ci, int Co);
 size_t cabinet_conv3x3s2_wgrad_workspace_bytes(int B, int Ci, int Co, int H, int W);
@@ -708,6 +713,9 @@ int cabinet_conv3x3s2_wgrad(const float* dy, const float* x, int B, int Ci, int 
                             void* workspace, size_t workspace_bytes, cabinet_stream_t stream);
 int cabinet_conv3x3s2_dgrad(const float* dy, const float* w, int B, int Ci, int Co, int H, int W, float* dx,
                             cabinet_stream_t stream);
+int cabinet_conv3x3s2_fwd_supported(int Ci, int Co);
+int cabinet_conv3x3s2_fwd(const float* x, const float* w, int B, int Ci, int Co, int H, int W, float* y,
+                          cabinet_stream_t stream);
 
 /* ------------------------------------------------------------------------- *
  * Optimizer tail (K16): gradient clipping, warm-up / poly SGD with momentum and
