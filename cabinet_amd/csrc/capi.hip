@@ -1295,7 +1295,7 @@ int cabinet_stem_conv_bn_bwd(const float* g, const float* z, const float* x, con
 static int check_pwconv(int B, int Ci, int Co, int P, const char* who) {
     if (B <= 0 || Ci <= 0 || Co <= 0 || P <= 0) return fail(CABINET_ERR_INVALID_ARG, "%s: non-positive dimension", who);
     if (!cabinet::pwconv_supported(Ci, Co, P))
-        return fail(CABINET_ERR_UNSUPPORTED, "%s: Ci=%d, Co=%d (multiples of 8, <= 120, block product <= 8)", who, Ci, Co);
+        return fail(CABINET_ERR_UNSUPPORTED, "%s: Ci=%d, Co=%d, P=%d (multiples of 8, <= 128, block product <= 8, P <= 2^21, max(Ci, Co) * P <= 2^28)", who, Ci, Co, P);
     return CABINET_OK;
 }
 

@@ -577,8 +577,9 @@ int cabinet_stem_conv_bn_bwd(const float* g, const float* z, const float* x, con
 /* ------------------------------------------------------------------------- *
  * Thin pointwise (1x1, bias-free, stride 1) convolution on large planes, streaming form:
  * y (B,Co,P) = W (Co,Ci) . x (B,Ci,P).  Replaces the nn.Conv2d(kernel_size=1) of the first MBConv blocks,
- * src/models/mobilenetv3.py:128-131,144-151, where the product is HBM-bound (Ci, Co <= 120).
- * Supported: Ci, Co multiples of 8, <= 120, ceil(Ci/32)*ceil(Co/32) <= 8 (cabinet_pwconv_supported).
+ * src/models/mobilenetv3.py:128-131,144-151, where the product is HBM-bound (Ci, Co <= 128).
+ * Supported: Ci, Co multiples of 8, <= 128, ceil(Ci/32)*ceil(Co/32) <= 8, P <= 2^21, max(Ci, Co) * P <= 2^28 (the kernels
+ *   address one image's operand with 32-bit byte offsets) (cabinet_pwconv_supported).
  *   bwd: dx = W^T dy (skipped if NULL), dw = sum_{b,p} dy (x) x (skipped if NULL); ordered slab sum, deterministic.
  * ------------------------------------------------------------------------- */
 int cabinet_pwconv_supported(int Ci, int Co, int P);
