@@ -133,6 +133,9 @@ SIGNATURES = {
     "cabinet_se_act_bwd_workspace_bytes": (_SZ, [_INT] * 3),
     "cabinet_se_act_bwd_reduce": (_INT, [_PTR] * 8 + [_INT] * 4 + [_PTR] * 2 + [_PTR, _SZ, _PTR]),
     "cabinet_se_act_bwd_coef": (_INT, [_PTR] * 3 + [_INT] * 4 + [_PTR] * 4 + [_PTR]),
+    "cabinet_se_act_bwd_mlp_supported": (_INT, [_INT] * 2),
+    "cabinet_se_act_bwd_mlp_workspace_bytes": (_SZ, [_INT] * 3),
+    "cabinet_se_act_bwd_mlp": (_INT, [_PTR] * 7 + [_INT] * 5 + [_PTR] * 9 + [_PTR, _SZ, _PTR]),
     "cabinet_se_act_bwd_dx": (_INT, [_PTR] * 9 + [_INT] * 4 + [_PTR] + [_PTR]),
     "cabinet_sgd_tail_workspace_bytes": (_SZ, [_INT]),
     "cabinet_sgd_tail_state_bytes": (_SZ, [_INT]),

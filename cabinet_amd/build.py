@@ -25,7 +25,7 @@ OBJ_DIR = os.path.join(PKG_DIR, "csrc", "build")
 LIB_PATH = os.path.join(PKG_DIR, "libcabinet_hip.so")
 ARCH = "gfx950"
 
-SOURCES = ["capi.hip", "cab_attn_fwd.hip", "cab_attn_bf16.hip", "cab_attn_bwd.hip", "ffm.hip", "ffm_bwd_fused.hip", "ffm_bwd_adj.hip", "ffm_fwd_fused.hip", "gemm_bf16.hip", "ohem.hip", "cab_local.hip", "cab_local_tiled.hip", "cab_qkv.hip", "cab_qkv_fused.hip", "bn_act.hip", "dwconv.hip", "stem_conv.hip", "pwconv.hip", "pwconv_wide.hip", "conv3x3_s2.hip", "small_gemm.hip", "conv3x3_wino.hip", "bn_cls.hip", "eval_tail.hip", "opt_tail.hip", "grad_accum.hip", "predict_tail.hip", "augment.hip", "augment_warp.hip"]
+SOURCES = ["capi.hip", "cab_attn_fwd.hip", "cab_attn_bf16.hip", "cab_attn_bwd.hip", "ffm.hip", "ffm_bwd_fused.hip", "ffm_bwd_adj.hip", "ffm_fwd_fused.hip", "gemm_bf16.hip", "ohem.hip", "cab_local.hip", "cab_local_tiled.hip", "cab_qkv.hip", "cab_qkv_fused.hip", "bn_act.hip", "se_mlp.hip", "dwconv.hip", "stem_conv.hip", "pwconv.hip", "pwconv_wide.hip", "conv3x3_s2.hip", "small_gemm.hip", "conv3x3_wino.hip", "bn_cls.hip", "eval_tail.hip", "opt_tail.hip", "grad_accum.hip", "predict_tail.hip", "augment.hip", "augment_warp.hip"]
 HEADERS = ["common.hpp", "cab_local.hpp", "cab_qkv.hpp", "blocks.hpp", "act.hpp", "bn_finalize.hpp", "slab_sum.hpp", "augment_taps.hpp", os.path.join("..", "..", "include", "cabinet_hip.h")]
 
 

@@ -84,6 +84,14 @@ hipError_t se_act_bwd_coef_run(const float* sums, const float* gate, const float
 hipError_t se_act_bwd_dx_run(const float* dy, const float* z, const float* mean, const float* invstd, const float* weight,
                              const float* bias, const float* gate, const float* ds_p, const float* coef, int B, int C, int P,
                              int act, float* dz, hipStream_t stream);
+// se_mlp.hip
+bool se_act_bwd_mlp_supported(int C, int Cs);
+size_t se_act_bwd_mlp_workspace(int B, int Cs);
+hipError_t se_act_bwd_mlp_run(const float* sums, const float* da2, const float* gate, const float* h1, const float* pooled,
+                              const float* w1, const float* w2, int B, int C, int Cs, int P, int training, float* dw1, float* db1,
+                              float* dw2, float* db2, float* ds, float* dweight, float* dbias, float* coef, float* ds_p, void* ws,
+                              hipStream_t stream);
+// bn_act.hip
 size_t gate_act_workspace(int rows, int P);
 hipError_t gate_act_fwd_run(const float* x, const float* gate, int rows, int P, int act, float* y, hipStream_t stream);
 hipError_t gate_act_bwd_run(const float* dy, const float* x, const float* gate, int rows, int P, int act, float* dx,
@@ -1175,6 +1183,30 @@ int cabinet_se_act_bwd_coef(const float* sums, const float* gate, const float* d
     return hip_status(cabinet::se_act_bwd_coef_run(sums, gate, ds, B, C, P, training, dbn_weight, dbn_bias, coef, ds_over_p,
                                                    static_cast<hipStream_t>(stream)),
                       "se_act_bwd_coef launch");
+}
+
+int cabinet_se_act_bwd_mlp_supported(int C, int Cs) { return C > 0 && Cs > 0 && cabinet::se_act_bwd_mlp_supported(C, Cs) ? 1 : 0; }
+
+size_t cabinet_se_act_bwd_mlp_workspace_bytes(int B, int C, int Cs) {
+    return B > 0 && C > 0 && Cs > 0 ? cabinet::se_act_bwd_mlp_workspace(B, Cs) : 0;
+}
+
+int cabinet_se_act_bwd_mlp(const float* sums, const float* da2, const float* gate, const float* h1, const float* pooled,
+                           const float* w1, const float* w2, int B, int C, int Cs, int P, int training, float* dw1, float* db1,
+                           float* dw2, float* db2, float* ds, float* dbn_weight, float* dbn_bias, float* coef, float* ds_over_p,
+                           void* workspace, size_t workspace_bytes, cabinet_stream_t stream) {
+    if (B <= 0 || C <= 0 || Cs <= 0 || P <= 0) return fail(CABINET_ERR_INVALID_ARG, "se_act_bwd_mlp: non-positive dimension");
+    if (!sums || !da2 || !gate || !h1 || !pooled || !w1 || !w2 || !dw1 || !db1 || !dw2 || !db2 || !ds || !dbn_weight || !dbn_bias ||
+        !coef || !ds_over_p)
+        return fail(CABINET_ERR_INVALID_ARG, "se_act_bwd_mlp: null tensor pointer");
+    if (!cabinet::se_act_bwd_mlp_supported(C, Cs))
+        return fail(CABINET_ERR_UNSUPPORTED, "se_act_bwd_mlp: C=%d / Cs=%d beyond the staged operand (max 1024)", C, Cs);
+    const size_t need = cabinet::se_act_bwd_mlp_workspace(B, Cs);
+    if (workspace_bytes < need || !workspace)
+        return fail(CABINET_ERR_WORKSPACE, "se_act_bwd_mlp: workspace %zu < %zu bytes", workspace_bytes, need);
+    return hip_status(cabinet::se_act_bwd_mlp_run(sums, da2, gate, h1, pooled, w1, w2, B, C, Cs, P, training, dw1, db1, dw2, db2, ds,
+                                                  dbn_weight, dbn_bias, coef, ds_over_p, workspace, static_cast<hipStream_t>(stream)),
+                      "se_act_bwd_mlp launch");
 }
 
 int cabinet_se_act_bwd_dx(const float* dy, const float* z, const float* mean, const float* invstd, const float* bn_weight,

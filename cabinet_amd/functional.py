@@ -1496,14 +1496,19 @@ def gate_act(x, gate, act=None):
 
 # --------------------------------------------------------------------------- BatchNorm -> SELayer -> act (SE tail)
 
+# CABINET_SE_MLP_FUSED=0: the MLP's backward between the two streaming passes goes back to the chain of torch ops followed by
+# cabinet_se_act_bwd_coef -- same-box A/B timing and the equality tests
+SE_MLP_FUSED = _os.environ.get("CABINET_SE_MLP_FUSED", "1") != "0"
+
 
 class _SeTail(torch.autograd.Function):
     """``act(se(bn(z)))`` with ``se(x) = x * hsig(fc2(relu(fc1(avgpool(x)))))`` as ONE autograd node.  The forward runs the
     very kernels of the composed form (K7 BatchNorm, the stock pool, the MLP, gate_act_fwd: bitwise the same output); the
     backward replaces gate_act_bwd + the pool's broadcast gradient + autograd's add + K7's reduce and dx by two passes over
-    (dy, z) (include/cabinet_hip.h: cabinet_se_act_bwd_*).  The MLP's backward is written out on (B, C) with autograd's
-    conventions at the clamp boundaries (ReLU: gradient where the output is > 0; ReLU6: where 0 < input < 6).  Saved for
-    backward: z, not the BatchNorm output."""
+    (dy, z) (include/cabinet_hip.h: cabinet_se_act_bwd_*).  Between them the MLP's backward on (B, C) and the BatchNorm
+    coefficients are two launches (cabinet_se_act_bwd_mlp; SE_MLP_FUSED off, or an MLP wider than its kernels stage: the chain
+    of torch ops and cabinet_se_act_bwd_coef), with autograd's conventions at the clamp boundaries (ReLU: gradient where the
+    output is > 0; ReLU6: where 0 < input < 6).  Saved for backward: z, not the BatchNorm output."""
 
     @staticmethod
     @torch.amp.custom_fwd(device_type="cuda", cast_inputs=torch.float32)
@@ -1551,17 +1556,32 @@ class _SeTail(torch.autograd.Function):
             rc = lib.cabinet_se_act_bwd_reduce(_ptr(g), _ptr(z), _ptr(mean), _ptr(invstd), _ptr(bn_w), _ptr(bn_b), _ptr(gate), _ptr(a2),
                                                B, C, P, fn_ctx.act, _ptr(sums), _ptr(da2), _ptr(ws), nbytes, stream)
         _lib.check(rc, "cabinet_se_act_bwd_reduce")
-        dw2, db2 = da2.t().mm(h1), da2.sum(0)
-        da1 = da2.mm(w2) * (h1 > 0)
-        dw1, db1 = da1.t().mm(pooled), da1.sum(0)
-        ds = da1.mm(w1)  # gradient of the pooled input
         dweight, dbias = torch.empty_like(bn_w), torch.empty_like(bn_b)
         coef = torch.empty((2, C), dtype=torch.float32, device=dev)
         ds_p = torch.empty((B, C), dtype=torch.float32, device=dev)
-        with torch.cuda.device(dev):
-            rc = lib.cabinet_se_act_bwd_coef(_ptr(sums), _ptr(gate), _ptr(ds), B, C, P, int(fn_ctx.training), _ptr(dweight),
-                                             _ptr(dbias), _ptr(coef), _ptr(ds_p), stream)
-        _lib.check(rc, "cabinet_se_act_bwd_coef")
+        Cs = w1.shape[0]
+        # the MLP's backward and the coefficients in two launches (csrc/se_mlp.hip); with CABINET_SE_MLP_FUSED=0, or for an MLP
+        # wider than those kernels stage (no SELayer of the two backbones is), the chain of torch ops and the coefficient kernel
+        if SE_MLP_FUSED and lib.cabinet_se_act_bwd_mlp_supported(C, Cs):
+            pooled, h1, w1, w2 = _f32c(pooled), _f32c(h1), _f32c(w1), _f32c(w2)
+            dw1, db1 = torch.empty_like(w1), torch.empty(Cs, dtype=torch.float32, device=dev)
+            dw2, db2 = torch.empty_like(w2), torch.empty(C, dtype=torch.float32, device=dev)
+            ds = torch.empty((B, C), dtype=torch.float32, device=dev)
+            mlp_ws, mlp_nbytes = _workspace(lib.cabinet_se_act_bwd_mlp_workspace_bytes(B, C, Cs), dev)
+            with torch.cuda.device(dev):
+                rc = lib.cabinet_se_act_bwd_mlp(_ptr(sums), _ptr(da2), _ptr(gate), _ptr(h1), _ptr(pooled), _ptr(w1), _ptr(w2), B, C,
+                                                Cs, P, int(fn_ctx.training), _ptr(dw1), _ptr(db1), _ptr(dw2), _ptr(db2), _ptr(ds),
+                                                _ptr(dweight), _ptr(dbias), _ptr(coef), _ptr(ds_p), _ptr(mlp_ws), mlp_nbytes, stream)
+            _lib.check(rc, "cabinet_se_act_bwd_mlp")
+        else:
+            dw2, db2 = da2.t().mm(h1), da2.sum(0)
+            da1 = da2.mm(w2) * (h1 > 0)
+            dw1, db1 = da1.t().mm(pooled), da1.sum(0)
+            ds = da1.mm(w1)  # gradient of the pooled input
+            with torch.cuda.device(dev):
+                rc = lib.cabinet_se_act_bwd_coef(_ptr(sums), _ptr(gate), _ptr(ds), B, C, P, int(fn_ctx.training), _ptr(dweight),
+                                                 _ptr(dbias), _ptr(coef), _ptr(ds_p), stream)
+            _lib.check(rc, "cabinet_se_act_bwd_coef")
         dz = torch.empty_like(z)
         with torch.cuda.device(dev):
             rc = lib.cabinet_se_act_bwd_dx(_ptr(g), _ptr(z), _ptr(mean), _ptr(invstd), _ptr(bn_w), _ptr(bn_b), _ptr(gate), _ptr(ds_p),

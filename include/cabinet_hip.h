@@ -514,6 +514,13 @@ int cabinet_gate_act_bwd(const float* dy, const float* x, const float* gate, int
  *            ds_over_p = ds / P, dbn_bias = sum_b (gate A + ds), dbn_weight = sum_b (gate X + ds_over_p S) and
  *            coef [2][C] = (dbn_bias, dbn_weight) / (B*P) (zeros when training == 0).
  *   dx     : dz = bn_weight * invstd * (gate * du + ds_over_p - coef[0][c] - xhat * coef[1][c]).
+ *   mlp    : the MLP's backward and coef in two launches, between reduce and dx.  h1 (B,Cs) the hidden layer after its ReLU,
+ *            pooled (B,C), w1 (Cs,C), w2 (C,Cs); from reduce's sums and da2:
+ *              dw2[c][j] = sum_b da2[b][c] h1[b][j],  db2[c] = sum_b da2[b][c],
+ *              da1[b][j] = sum_c da2[b][c] w2[c][j] where h1[b][j] > 0, else 0   (workspace),
+ *              dw1[j][c] = sum_b da1[b][j] pooled[b][c],  db1[j] = sum_b da1[b][j],  ds[b][c] = sum_j da1[b][j] w1[j][c],
+ *            then coef's outputs from that ds, bit for bit what cabinet_se_act_bwd_coef gives for it.  C and Cs up to 1024
+ *            (cabinet_se_act_bwd_mlp_supported; CABINET_ERR_UNSUPPORTED beyond: the caller forms ds itself and calls coef), any B.
  * ------------------------------------------------------------------------- */
 size_t cabinet_se_act_bwd_workspace_bytes(int B, int C, int P);
 int cabinet_se_act_bwd_reduce(const float* dy, const float* z, const float* mean, const float* invstd, const float* bn_weight,
@@ -521,6 +528,12 @@ int cabinet_se_act_bwd_reduce(const float* dy, const float* z, const float* mean
                               float* sums, float* da2, void* workspace, size_t workspace_bytes, cabinet_stream_t stream);
 int cabinet_se_act_bwd_coef(const float* sums, const float* gate, const float* ds, int B, int C, int P, int training,
                             float* dbn_weight, float* dbn_bias, float* coef, float* ds_over_p, cabinet_stream_t stream);
+int cabinet_se_act_bwd_mlp_supported(int C, int Cs); /* 1 / 0 */
+size_t cabinet_se_act_bwd_mlp_workspace_bytes(int B, int C, int Cs);
+int cabinet_se_act_bwd_mlp(const float* sums, const float* da2, const float* gate, const float* h1, const float* pooled,
+                           const float* w1, const float* w2, int B, int C, int Cs, int P, int training, float* dw1, float* db1,
+                           float* dw2, float* db2, float* ds, float* dbn_weight, float* dbn_bias, float* coef, float* ds_over_p,
+                           void* workspace, size_t workspace_bytes, cabinet_stream_t stream);
 int cabinet_se_act_bwd_dx(const float* dy, const float* z, const float* mean, const float* invstd, const float* bn_weight,
                           const float* bn_bias, const float* gate, const float* ds_over_p, const float* coef,
                           int B, int C, int P, int act, float* dz, cabinet_stream_t stream);
