@@ -95,6 +95,11 @@ SIGNATURES = {
     "cabinet_stem_conv_bn_bwd": (_INT, [_PTR] * 7 + [_INT] * 4 + [_PTR] * 3 + [_PTR, _SZ, _PTR]),
     "cabinet_pwconv_supported": (_INT, [_INT] * 3),
     "cabinet_pwconv_fwd": (_INT, [_PTR] * 2 + [_INT] * 4 + [_PTR] + [_PTR]),
+    "cabinet_pw_bn_bwd_supported": (_INT, [_INT] * 3),
+    "cabinet_pw_bn_act_bwd_workspace_bytes": (_SZ, [_INT] * 4),
+    "cabinet_pw_bn_act_bwd": (_INT, [_PTR] * 8 + [_INT] * 6 + [_PTR] * 4 + [_PTR, _SZ, _PTR]),
+    "cabinet_pw_bn_dwconv_bwd_workspace_bytes": (_SZ, [_INT] * 7),
+    "cabinet_pw_bn_dwconv_bwd": (_INT, [_PTR] * 9 + [_INT] * 9 + [_PTR] * 5 + [_PTR, _SZ, _PTR]),
     "cabinet_pwconv_bwd_workspace_bytes": (_SZ, [_INT] * 4),
     "cabinet_pwconv_bwd": (_INT, [_PTR] * 3 + [_INT] * 4 + [_PTR] * 2 + [_PTR, _SZ, _PTR]),
     "cabinet_pwconv_wide_supported": (_INT, [_INT] * 3),

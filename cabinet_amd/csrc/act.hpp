@@ -53,5 +53,15 @@ hipError_t bn_bwd_tail_run(const float* part, int nt, const float* dy, const flo
 hipError_t bn_act_bwd_stats_run(const float* dy, const float* x, const float* weight, const float* bias,
                                 const float* save_mean, const float* save_invstd, int B, int C, int P, int act, int training,
                                 float* dweight, float* dbias, void* ws, const float** coef, hipStream_t stream);
+hipError_t bn_bwd_finalize_run(const float* part, int nt, int C, double count, int training, float* dweight, float* dbias,
+                               float* coef, hipStream_t stream);
+
+// pwconv_wide.hip, BN form: backward of a thin 1x1 convolution z = W x and the BatchNorm (+activation) behind it in one walk over
+// g, z, x -- dz is formed while staging and never stored.  coef: [2][Co] finished coefficients; dx / dw may be null.
+bool pw_bn_bwd_supported(int Ci, int Co, int P);
+size_t pw_bn_bwd_slab_bytes(int B, int Ci, int Co, int P);
+hipError_t pw_bn_bwd_run(const float* g, const float* z, const float* x, const float* w, const float* mean, const float* invstd,
+                         const float* gamma, const float* beta, const float* coef, int B, int Ci, int Co, int P, int act,
+                         float* dx, float* dw, void* slab_ws, hipStream_t stream);
 
 }  // namespace cabinet

@@ -575,6 +575,14 @@ hipError_t bn_act_bwd_stats_run(const float* dy, const float* x, const float* we
     return hipGetLastError();
 }
 
+// the stand-alone finalize alone, on partials a producer kernel wrote (K8's backward): dweight, dbias and coef [2][C]
+hipError_t bn_bwd_finalize_run(const float* part, int nt, int C, double count, int training, float* dweight, float* dbias,
+                               float* coef, hipStream_t stream) {
+    hipLaunchKernelGGL(bn_act_bwd_finalize_kernel, dim3(C), dim3(BA_T), 0, stream, part, nt, C, count, training, dweight, dbias,
+                       coef);
+    return hipGetLastError();
+}
+
 size_t gate_act_workspace(int rows, int P) { return align_up((size_t)rows * ba_chunks(P) * sizeof(float), 256); }
 
 hipError_t gate_act_fwd_run(const float* x, const float* gate, int rows, int P, int act, float* y, hipStream_t stream) {

@@ -132,6 +132,17 @@ hipError_t stem_conv_bn_bwd_run(const float* g, const float* z, const float* x, 
                                 float* dbn_weight, float* dbn_bias, void* ws, hipStream_t stream);
 hipError_t stem_conv_wrw_run(const float* dy, const float* x, int B, int H, int W, float* dw, void* ws,
                              hipStream_t stream);
+// pwconv_wide.hip / dwconv.hip: the BN form (thin convolution + BatchNorm backward in one walk)
+bool pw_bn_bwd_supported(int Ci, int Co, int P);
+size_t pw_bn_act_bwd_workspace(int B, int Ci, int Co, int P);
+hipError_t pw_bn_act_bwd_run(const float* g, const float* z, const float* x, const float* w, const float* bn_w, const float* bn_b,
+                             const float* save_mean, const float* save_invstd, int B, int Ci, int Co, int P, int act, int training,
+                             float* dx, float* dw, float* dbn_w, float* dbn_b, void* ws, hipStream_t stream);
+size_t pw_bn_dwconv_bwd_workspace(int B, int Ci, int C, int H, int W, int K);
+hipError_t pw_bn_dwconv_bwd_run(const float* dy, const float* z, const float* x, const float* pw_w, const float* bn_w,
+                                const float* bn_b, const float* save_mean, const float* save_invstd, const float* w, int B, int Ci,
+                                int C, int H, int W, int K, int S, int act, int training, float* dx, float* dpw_w, float* dbn_w,
+                                float* dbn_b, float* dw, void* ws, hipStream_t stream);
 // pwconv_wide.hip
 bool pwconv_wide_supported(int Ci, int Co, int P);
 size_t pwconv_wide_wgrad_workspace(int B, int Ci, int Co, int P);
@@ -1356,6 +1367,70 @@ int cabinet_pwconv_bwd(const float* dy, const float* x, const float* w, int B, i
         return fail(CABINET_ERR_WORKSPACE, "pwconv_bwd: workspace %zu < %zu bytes", workspace_bytes, need);
     return hip_status(cabinet::pwconv_bwd_run(dy, x, w, B, Ci, Co, P, dx, dw, workspace, static_cast<hipStream_t>(stream)),
                       "pwconv_bwd launch");
+}
+
+// ------------------------------------------------------ thin pointwise convolution + BatchNorm, backward in one walk
+static int check_pw_bn(int B, int Ci, int Co, int P, int act, const char* who) {
+    if (int rc = check_bn_act(B, Co, P, act, who)) return rc;
+    if (Ci <= 0) return fail(CABINET_ERR_INVALID_ARG, "%s: non-positive dimension", who);
+    if (!cabinet::pw_bn_bwd_supported(Ci, Co, P))
+        return fail(CABINET_ERR_UNSUPPORTED, "%s: Ci=%d, Co=%d, P=%d (multiples of 8, <= 96, P <= 2^21)", who, Ci, Co, P);
+    return CABINET_OK;
+}
+
+int cabinet_pw_bn_bwd_supported(int Ci, int Co, int P) {
+    return Ci > 0 && Co > 0 && P > 0 && cabinet::pw_bn_bwd_supported(Ci, Co, P) ? 1 : 0;
+}
+
+size_t cabinet_pw_bn_act_bwd_workspace_bytes(int B, int Ci, int Co, int P) {
+    if (B <= 0 || Ci <= 0 || Co <= 0 || P <= 0 || !cabinet::pw_bn_bwd_supported(Ci, Co, P)) return 0;
+    return cabinet::pw_bn_act_bwd_workspace(B, Ci, Co, P);
+}
+
+int cabinet_pw_bn_act_bwd(const float* g, const float* z, const float* x, const float* pw_weight, const float* bn_weight,
+                          const float* bn_bias, const float* save_mean, const float* save_invstd, int B, int Ci, int Co, int P,
+                          int act, int training, float* dx, float* dpw_weight, float* dbn_weight, float* dbn_bias,
+                          void* workspace, size_t workspace_bytes, cabinet_stream_t stream) {
+    if (int rc = check_pw_bn(B, Ci, Co, P, act, "pw_bn_act_bwd")) return rc;
+    if (!g || !z || !pw_weight || !bn_weight || !bn_bias || !save_mean || !save_invstd || !dbn_weight || !dbn_bias ||
+        (dpw_weight && !x))
+        return fail(CABINET_ERR_INVALID_ARG, "pw_bn_act_bwd: null tensor pointer");
+    if (P % 4 == 0) {  // the BatchNorm reduce reads g and z 16 bytes at a time there; x, dx and the weights may start anywhere
+        CABINET_REQUIRE_ALIGNED("pw_bn_act_bwd", g, z);
+    }
+    const size_t need = cabinet::pw_bn_act_bwd_workspace(B, Ci, Co, P);
+    if (!workspace || workspace_bytes < need)
+        return fail(CABINET_ERR_WORKSPACE, "pw_bn_act_bwd: workspace %zu < %zu bytes", workspace_bytes, need);
+    return hip_status(cabinet::pw_bn_act_bwd_run(g, z, x, pw_weight, bn_weight, bn_bias, save_mean, save_invstd, B, Ci, Co, P, act,
+                                                 training, dx, dpw_weight, dbn_weight, dbn_bias, workspace,
+                                                 static_cast<hipStream_t>(stream)),
+                      "pw_bn_act_bwd launch");
+}
+
+size_t cabinet_pw_bn_dwconv_bwd_workspace_bytes(int B, int Ci, int C, int H, int W, int K, int stride) {
+    if (B <= 0 || Ci <= 0 || C <= 0 || H <= 0 || W <= 0 || !cabinet::dwconv_supported(K, stride) ||
+        !cabinet::pw_bn_bwd_supported(Ci, C, H * W))
+        return 0;
+    return cabinet::pw_bn_dwconv_bwd_workspace(B, Ci, C, H, W, K);
+}
+
+int cabinet_pw_bn_dwconv_bwd(const float* dy, const float* z, const float* x, const float* pw_weight, const float* bn_weight,
+                             const float* bn_bias, const float* save_mean, const float* save_invstd, const float* conv_weight,
+                             int B, int Ci, int C, int H, int W, int K, int stride, int act, int training, float* dx,
+                             float* dpw_weight, float* dbn_weight, float* dbn_bias, float* dconv_weight, void* workspace,
+                             size_t workspace_bytes, cabinet_stream_t stream) {
+    if (int rc = check_dwconv(B, C, H, W, K, stride, "pw_bn_dwconv_bwd")) return rc;
+    if (int rc = check_pw_bn(B, Ci, C, H * W, act, "pw_bn_dwconv_bwd")) return rc;
+    if (!dy || !z || !pw_weight || !bn_weight || !bn_bias || !save_mean || !save_invstd || !conv_weight || !dbn_weight ||
+        !dbn_bias || !dconv_weight || (dpw_weight && !x))
+        return fail(CABINET_ERR_INVALID_ARG, "pw_bn_dwconv_bwd: null tensor pointer");
+    const size_t need = cabinet::pw_bn_dwconv_bwd_workspace(B, Ci, C, H, W, K);
+    if (!workspace || workspace_bytes < need)
+        return fail(CABINET_ERR_WORKSPACE, "pw_bn_dwconv_bwd: workspace %zu < %zu bytes", workspace_bytes, need);
+    return hip_status(cabinet::pw_bn_dwconv_bwd_run(dy, z, x, pw_weight, bn_weight, bn_bias, save_mean, save_invstd, conv_weight, B,
+                                                    Ci, C, H, W, K, stride, act, training, dx, dpw_weight, dbn_weight, dbn_bias,
+                                                    dconv_weight, workspace, static_cast<hipStream_t>(stream)),
+                      "pw_bn_dwconv_bwd launch");
 }
 
 // ------------------------------------------------------ wide pointwise convolution: weight gradient

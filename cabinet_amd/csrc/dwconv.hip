@@ -787,4 +787,30 @@ hipError_t bn_dwconv_bwd_run(const float* dy, const float* z, const float* bn_w,
                            training, dz, dbn_w, dbn_b, at(L.coef), stream);
 }
 
+// ---- thin 1x1 convolution -> BatchNorm (+activation) -> depthwise convolution, backward: what bn_dwconv_bwd_run runs up to the
+// BatchNorm partials, the stand-alone finalize on them, then K10's BN-form kernel with g = da -- the BatchNorm's dz (its dx pass)
+// and the 1x1 convolution's two backward kernels that read it are one walk (pwconv_wide.hip).
+size_t pw_bn_dwconv_bwd_workspace(int B, int Ci, int C, int H, int W, int K) {
+    return bn_dw_layout(B, C, H, W, K).total + pw_bn_bwd_slab_bytes(B, Ci, C, H * W);
+}
+
+hipError_t pw_bn_dwconv_bwd_run(const float* dy, const float* z, const float* x, const float* pw_w, const float* bn_w,
+                                const float* bn_b, const float* save_mean, const float* save_invstd, const float* w, int B, int Ci,
+                                int C, int H, int W, int K, int S, int act, int training, float* dx, float* dpw_w, float* dbn_w,
+                                float* dbn_b, float* dw, void* ws, hipStream_t stream) {
+    const BnDwWs L = bn_dw_layout(B, C, H, W, K);
+    char* base = static_cast<char*>(ws);
+    auto at = [&](size_t o) { return reinterpret_cast<float*>(base + o); };
+    DwShape s{B, C, H, W, 0, 0};
+    out_size(H, W, K, S, s.Ho, s.Wo);
+    hipError_t e = bwd_dispatch(dy, z, w, s, K, S, BnFold{save_mean, save_invstd, bn_w, bn_b, act}, at(L.da), dw, at(L.part),
+                                at(L.bnpart), stream);
+    if (e != hipSuccess) return e;
+    e = bn_bwd_finalize_run(at(L.bnpart), B * bwd_tiles(H, W), C, (double)B * (double)(H * W), training, dbn_w, dbn_b, at(L.coef),
+                            stream);
+    if (e != hipSuccess) return e;
+    return pw_bn_bwd_run(at(L.da), z, x, pw_w, save_mean, save_invstd, bn_w, bn_b, at(L.coef), B, Ci, C, H * W, act, dx, dpw_w,
+                         base + L.total, stream);
+}
+
 }  // namespace cabinet

@@ -1312,6 +1312,11 @@ def bn_act(x, bn, act=None, residual=None, conv_part=None):
     if conv_part is not None:
         return _BnAct.apply(x, bn.weight, bn.bias, bn.running_mean, bn.running_var, _ACT_CODES[act], training, momentum,
                             bn.eps, residual, conv_part)
+    src = _pw_bn_source(x, bn)
+    if src is not None:  # x = pwconv(...): one backward for the convolution and this BatchNorm (same forward calls)
+        args = (src[0], src[1], x.detach(), bn.weight, bn.bias, bn.running_mean, bn.running_var, _ACT_CODES[act], training,
+                momentum, bn.eps)
+        return _PwBnAct.apply(*args, residual) if residual is not None else _PwBnAct.apply(*args)
     return _BnAct.apply(x, bn.weight, bn.bias, bn.running_mean, bn.running_var, _ACT_CODES[act], training, momentum,
                         bn.eps, residual)
 
@@ -1656,6 +1661,10 @@ def bn_act_dwconv(z, bn, act, conv):
     if act not in _ACT_CODES:
         raise RuntimeError(f"bn_act_dwconv: unknown activation {act!r}")
     training, momentum = _bn_step(bn)
+    src = _pw_bn_source(z, bn, conv.weight)
+    if src is not None:  # z = pwconv(...): one backward for that convolution and this BatchNorm (same forward calls)
+        return _PwBnActDwConv.apply(src[0], src[1], z.detach(), bn.weight, bn.bias, bn.running_mean, bn.running_var, conv.weight,
+                                    _ACT_CODES[act], conv.stride[0], training, momentum, bn.eps)
     return _BnActDwConv.apply(z, bn.weight, bn.bias, bn.running_mean, bn.running_var, conv.weight, _ACT_CODES[act],
                               conv.stride[0], training, momentum, bn.eps)
 
@@ -1826,7 +1835,127 @@ def pwconv(x, conv):
     """Thin pointwise convolution of a device tensor with the weights of ``conv`` (see pwconv_supported)."""
     if not x.is_cuda:
         raise RuntimeError("pwconv: device tensors only")
-    return _PwConv.apply(x, conv.weight)
+    y = _PwConv.apply(x, conv.weight)
+    if PW_BN_BWD_FUSED and y.requires_grad:
+        y._pw_src = (x, conv.weight)  # for the BatchNorm that consumes y: see _pw_bn_source
+    return y
+
+
+# CABINET_PW_BN_BWD_FUSED=0: a thin 1x1 convolution and the BatchNorm behind it go back to their two backward nodes -- same-box A/B
+# timing and the equality tests
+PW_BN_BWD_FUSED = _os.environ.get("CABINET_PW_BN_BWD_FUSED", "1") != "0"
+
+
+def _pw_bn_source(z, bn, *more_params):
+    """``(x, weight)`` of the thin 1x1 convolution (:func:`pwconv`) that produced ``z`` when its backward can be taken together
+    with the backward of the BatchNorm ``bn`` that consumes ``z`` (cabinet_pw_bn_*_bwd), else None: the flag is on, a graph is
+    being recorded outside autocast, every parameter involved is trainable fp32 and the shape is one the kernel takes."""
+    src = getattr(z, "_pw_src", None)
+    if src is None or not PW_BN_BWD_FUSED or not torch.is_grad_enabled() or torch.is_autocast_enabled():
+        return None
+    x, w = src
+    params = (w, bn.weight, bn.bias) + more_params
+    if not all(p.requires_grad and p.dtype == torch.float32 for p in params):
+        return None
+    if not (z.dim() == 4 and z.dtype == torch.float32 and x.dtype == torch.float32 and z.is_contiguous() and x.is_contiguous()):
+        return None
+    if not _lib.load().cabinet_pw_bn_bwd_supported(w.shape[1], w.shape[0], z.shape[2] * z.shape[3]):
+        return None
+    return x, w
+
+
+class _PwBnAct(torch.autograd.Function):
+    """act(bn(z)) [+ residual] for z = pwconv(x, w), as the node of BOTH: the forward is K7's call on z (the convolution has run,
+    its own node receives no gradient and never runs), the backward is cabinet_pw_bn_act_bwd -- the BatchNorm's input gradient
+    (B, Co, H, W) is never written; the weight-gradient kernel forms it while staging and multiplies it by W^T as well."""
+
+    @staticmethod
+    def forward(fn_ctx, x, w, z, bn_w, bn_b, run_mean, run_var, act, training, momentum, eps, residual=None):
+        lib = _lib.load()
+        bn_w, bn_b = _f32c(bn_w), _f32c(bn_b)
+        residual = _f32c(residual) if residual is not None else None
+        B, C, P = z.shape[0], z.shape[1], z.shape[2] * z.shape[3]
+        y = torch.empty_like(z)
+        mean = torch.empty(C, dtype=torch.float32, device=z.device)
+        invstd = torch.empty(C, dtype=torch.float32, device=z.device)
+        ws, nbytes = _workspace(lib.cabinet_bn_act_workspace_bytes(B, C, P), z.device)
+        with torch.cuda.device(z.device):
+            rc = lib.cabinet_bn_act_fwd(_ptr(z), _ptr(bn_w), _ptr(bn_b), _ptr(run_mean), _ptr(run_var), _ptr(residual), B, C, P,
+                                        act, int(training), float(momentum), float(eps), _ptr(y), _ptr(mean), _ptr(invstd),
+                                        _ptr(ws), nbytes, _stream_handle(z.device))
+        _lib.check(rc, "cabinet_bn_act_fwd")
+        fn_ctx.save_for_backward(x, _f32c(w).view(w.shape[0], w.shape[1]), z, bn_w, bn_b, mean, invstd)
+        fn_ctx.meta = (act, bool(training), w.shape)
+        return y
+
+    @staticmethod
+    def backward(fn_ctx, g):
+        lib = _lib.load()
+        x, w2, z, bn_w, bn_b, mean, invstd = fn_ctx.saved_tensors
+        act, training, w_shape = fn_ctx.meta
+        need = fn_ctx.needs_input_grad
+        g = _f32c(g)
+        Co, Ci = w2.shape
+        B, P = z.shape[0], z.shape[2] * z.shape[3]
+        dx = torch.empty_like(x) if need[0] else None
+        dw = torch.empty_like(w2) if need[1] else None
+        dgam, dbet = torch.empty_like(bn_w), torch.empty_like(bn_b)
+        ws, nbytes = _workspace(lib.cabinet_pw_bn_act_bwd_workspace_bytes(B, Ci, Co, P), z.device)
+        with torch.cuda.device(z.device):
+            rc = lib.cabinet_pw_bn_act_bwd(_ptr(g), _ptr(z), _ptr(x), _ptr(w2), _ptr(bn_w), _ptr(bn_b), _ptr(mean), _ptr(invstd),
+                                           B, Ci, Co, P, act, int(training), _ptr(dx), _ptr(dw), _ptr(dgam), _ptr(dbet),
+                                           _ptr(ws), nbytes, _stream_handle(z.device))
+        _lib.check(rc, "cabinet_pw_bn_act_bwd")
+        grads = (dx, dw.view(w_shape) if dw is not None else None, None, dgam, dbet) + (None,) * 6
+        if len(need) > 11:  # called with the shortcut: d(residual) = dy
+            grads += (g if need[11] else None,)
+        return grads
+
+
+class _PwBnActDwConv(torch.autograd.Function):
+    """conv(act(bn(z))) for z = pwconv(x, w) and a depthwise ``conv``, as the node of both: the forward is
+    cabinet_bn_dwconv_fwd on z, the backward cabinet_pw_bn_dwconv_bwd (see _PwBnAct)."""
+
+    @staticmethod
+    def forward(fn_ctx, x, w, z, bn_w, bn_b, run_mean, run_var, conv_w, act, stride, training, momentum, eps):
+        lib = _lib.load()
+        bn_w, bn_b, cw = _f32c(bn_w), _f32c(bn_b), _f32c(conv_w)
+        B, C, H, W = z.shape
+        K = cw.shape[-1]
+        Ho, Wo = (H + 2 * (K // 2) - K) // stride + 1, (W + 2 * (K // 2) - K) // stride + 1
+        y = torch.empty((B, C, Ho, Wo), dtype=torch.float32, device=z.device)
+        mean = torch.empty(C, dtype=torch.float32, device=z.device)
+        invstd = torch.empty(C, dtype=torch.float32, device=z.device)
+        ws, nbytes = _workspace(lib.cabinet_bn_dwconv_fwd_workspace_bytes(B, C, H, W), z.device)
+        with torch.cuda.device(z.device):
+            rc = lib.cabinet_bn_dwconv_fwd(_ptr(z), _ptr(bn_w), _ptr(bn_b), _ptr(run_mean), _ptr(run_var), _ptr(cw), B, C,
+                                           H, W, K, stride, act, int(training), float(momentum), float(eps), _ptr(y),
+                                           _ptr(mean), _ptr(invstd), _ptr(ws), nbytes, _stream_handle(z.device))
+        _lib.check(rc, "cabinet_bn_dwconv_fwd")
+        fn_ctx.save_for_backward(x, _f32c(w).view(w.shape[0], w.shape[1]), z, bn_w, bn_b, cw, mean, invstd)
+        fn_ctx.meta = (act, stride, bool(training), w.shape)
+        return y
+
+    @staticmethod
+    def backward(fn_ctx, g):
+        lib = _lib.load()
+        x, w2, z, bn_w, bn_b, cw, mean, invstd = fn_ctx.saved_tensors
+        act, stride, training, w_shape = fn_ctx.meta
+        need = fn_ctx.needs_input_grad
+        g = _f32c(g)
+        B, C, H, W = z.shape
+        Ci, K = w2.shape[1], cw.shape[-1]
+        dx = torch.empty_like(x) if need[0] else None
+        dw = torch.empty_like(w2) if need[1] else None
+        dgam, dbet, dcw = torch.empty_like(bn_w), torch.empty_like(bn_b), torch.empty_like(cw)
+        ws, nbytes = _workspace(lib.cabinet_pw_bn_dwconv_bwd_workspace_bytes(B, Ci, C, H, W, K, stride), z.device)
+        with torch.cuda.device(z.device):
+            rc = lib.cabinet_pw_bn_dwconv_bwd(_ptr(g), _ptr(z), _ptr(x), _ptr(w2), _ptr(bn_w), _ptr(bn_b), _ptr(mean),
+                                              _ptr(invstd), _ptr(cw), B, Ci, C, H, W, K, stride, act, int(training), _ptr(dx),
+                                              _ptr(dw), _ptr(dgam), _ptr(dbet), _ptr(dcw), _ptr(ws), nbytes,
+                                              _stream_handle(z.device))
+        _lib.check(rc, "cabinet_pw_bn_dwconv_bwd")
+        return (dx, dw.view(w_shape) if dw is not None else None, None, dgam, dbet, None, None, dcw) + (None,) * 5
 
 
 # --------------------------------------------------------------------------- wide pointwise convolution: weight gradient (K14)

@@ -602,6 +602,31 @@ int cabinet_pwconv_bwd(const float* dy, const float* x, const float* w, int B, i
                        float* dx, float* dw, void* workspace, size_t workspace_bytes, cabinet_stream_t stream);
 
 /* ------------------------------------------------------------------------- *
+ * Backward of a thin pointwise convolution z = W x (as cabinet_pwconv_fwd) TOGETHER with the BatchNorm (+activation) that
+ * consumes z, src/models/mobilenetv3.py:128-152: the BatchNorm's input gradient dz is formed while the weight-gradient kernel
+ * stages its operands, feeds dw = sum dz (x) x and dx = W^T dz from the LDS, and is never written.  One tile: Ci, Co
+ * multiples of 8, <= 96, P as cabinet_pwconv_wide_supported (cabinet_pw_bn_bwd_supported).  dx and / or dw may be NULL (that
+ * product is skipped).  Ordered sums, no atomics, deterministic.
+ *   cabinet_pw_bn_act_bwd     : z -> act(bn(z)) (cabinet_bn_act_fwd; a shortcut's gradient is g itself).  g (B,Co,P) is the
+ *       gradient at the activation's output.  dbn_weight / dbn_bias are bit for bit cabinet_bn_act_bwd's, dw is
+ *       cabinet_pwconv_bwd's applied to that call's dx.  g, z 16-byte aligned where P % 4 == 0.
+ *   cabinet_pw_bn_dwconv_bwd  : z -> depthwise conv(act(bn(z))) (cabinet_bn_dwconv_fwd).  dy (B,C,Ho,Wo); dconv_weight,
+ *       dbn_weight, dbn_bias are bit for bit cabinet_bn_dwconv_bwd's.  x (B,Ci,H,W), pw_weight (C,Ci).
+ * ------------------------------------------------------------------------- */
+int cabinet_pw_bn_bwd_supported(int Ci, int Co, int P);
+size_t cabinet_pw_bn_act_bwd_workspace_bytes(int B, int Ci, int Co, int P);
+int cabinet_pw_bn_act_bwd(const float* g, const float* z, const float* x, const float* pw_weight, const float* bn_weight,
+                          const float* bn_bias, const float* save_mean, const float* save_invstd, int B, int Ci, int Co, int P,
+                          int act, int training, float* dx, float* dpw_weight, float* dbn_weight, float* dbn_bias,
+                          void* workspace, size_t workspace_bytes, cabinet_stream_t stream);
+size_t cabinet_pw_bn_dwconv_bwd_workspace_bytes(int B, int Ci, int C, int H, int W, int K, int stride);
+int cabinet_pw_bn_dwconv_bwd(const float* dy, const float* z, const float* x, const float* pw_weight, const float* bn_weight,
+                             const float* bn_bias, const float* save_mean, const float* save_invstd, const float* conv_weight,
+                             int B, int Ci, int C, int H, int W, int K, int stride, int act, int training, float* dx,
+                             float* dpw_weight, float* dbn_weight, float* dbn_bias, float* dconv_weight,
+                             void* workspace, size_t workspace_bytes, cabinet_stream_t stream);
+
+/* ------------------------------------------------------------------------- *
  * Weight gradient of the WIDE pointwise (1x1, bias-free, stride 1) convolutions, the ones cabinet_pwconv_supported leaves
  * to the stock operator (src/models/mobilenetv3.py:128-131,144-151,193, cabinet.py:114): NCHW in, no layout copy,
  *   dw (Co,Ci) = sum_{b,p} dy (B,Co,P) (x) x (B,Ci,P)
