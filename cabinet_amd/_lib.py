@@ -94,8 +94,10 @@ SIGNATURES = {
     "cabinet_stem_conv_bn_bwd_workspace_bytes": (_SZ, [_INT] * 3),
     "cabinet_stem_conv_bn_bwd": (_INT, [_PTR] * 7 + [_INT] * 4 + [_PTR] * 3 + [_PTR, _SZ, _PTR]),
     "cabinet_pwconv_supported": (_INT, [_INT] * 3),
+    "cabinet_pwconv_stream_plan": (_INT, [_INT] * 6 + [_PTR]),
     "cabinet_pwconv_fwd": (_INT, [_PTR] * 2 + [_INT] * 4 + [_PTR] + [_PTR]),
     "cabinet_pw_bn_bwd_supported": (_INT, [_INT] * 3),
+    "cabinet_pw_bn_bwd_plan": (_INT, [_INT] * 5 + [_PTR]),
     "cabinet_pw_bn_act_bwd_workspace_bytes": (_SZ, [_INT] * 4),
     "cabinet_pw_bn_act_bwd": (_INT, [_PTR] * 8 + [_INT] * 6 + [_PTR] * 4 + [_PTR, _SZ, _PTR]),
     "cabinet_pw_bn_dwconv_bwd_workspace_bytes": (_SZ, [_INT] * 7),
@@ -103,6 +105,7 @@ SIGNATURES = {
     "cabinet_pwconv_bwd_workspace_bytes": (_SZ, [_INT] * 4),
     "cabinet_pwconv_bwd": (_INT, [_PTR] * 3 + [_INT] * 4 + [_PTR] * 2 + [_PTR, _SZ, _PTR]),
     "cabinet_pwconv_wide_supported": (_INT, [_INT] * 3),
+    "cabinet_pwconv_wide_plan": (_INT, [_INT] * 4 + [_PTR]),
     "cabinet_pwconv_wide_wgrad_workspace_bytes": (_SZ, [_INT] * 4),
     "cabinet_pwconv_wide_wgrad": (_INT, [_PTR] * 2 + [_INT] * 4 + [_PTR] + [_PTR, _SZ, _PTR]),
     "cabinet_conv3x3s2_supported": (_INT, [_INT] * 2),

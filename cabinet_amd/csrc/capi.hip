@@ -134,6 +134,7 @@ hipError_t stem_conv_wrw_run(const float* dy, const float* x, int B, int H, int 
                              hipStream_t stream);
 // pwconv_wide.hip / dwconv.hip: the BN form (thin convolution + BatchNorm backward in one walk)
 bool pw_bn_bwd_supported(int Ci, int Co, int P);
+void pw_bn_bwd_plan_query(int B, int Ci, int Co, int P, unsigned dx_align, int out[5]);
 size_t pw_bn_act_bwd_workspace(int B, int Ci, int Co, int P);
 hipError_t pw_bn_act_bwd_run(const float* g, const float* z, const float* x, const float* w, const float* bn_w, const float* bn_b,
                              const float* save_mean, const float* save_invstd, int B, int Ci, int Co, int P, int act, int training,
@@ -145,6 +146,7 @@ hipError_t pw_bn_dwconv_bwd_run(const float* dy, const float* z, const float* x,
                                 float* dbn_b, float* dw, void* ws, hipStream_t stream);
 // pwconv_wide.hip
 bool pwconv_wide_supported(int Ci, int Co, int P);
+void pwconv_wide_plan_query(int B, int Ci, int Co, int P, int out[5]);
 size_t pwconv_wide_wgrad_workspace(int B, int Ci, int Co, int P);
 hipError_t pwconv_wide_wgrad_run(const float* dy, const float* x, int B, int Ci, int Co, int P, float* dw, void* ws,
                                  hipStream_t stream);
@@ -161,6 +163,7 @@ long long conv3x3s2_fwd_workgroups(int B, int H, int W);
 hipError_t conv3x3s2_fwd_run(const float* x, const float* w, int B, int H, int W, float* y, hipStream_t stream);
 // pwconv.hip
 bool pwconv_supported(int Ci, int Co, int P);
+void pwconv_stream_plan_query(int B, int M, int K, int P, unsigned x_align, unsigned y_align, int out[4]);
 size_t pwconv_bwd_workspace(int B, int Ci, int Co, int P);
 hipError_t pwconv_fwd_run(const float* x, const float* w, int B, int Ci, int Co, int P, float* y, hipStream_t stream);
 hipError_t pwconv_bwd_run(const float* dy, const float* x, const float* w, int B, int Ci, int Co, int P, float* dx,
@@ -1346,6 +1349,13 @@ int cabinet_pwconv_supported(int Ci, int Co, int P) {
     return Ci > 0 && Co > 0 && P > 0 && cabinet::pwconv_supported(Ci, Co, P) ? 1 : 0;
 }
 
+int cabinet_pwconv_stream_plan(int B, int M, int K, int P, int x_align_bytes, int y_align_bytes, int out[4]) {
+    if (int rc = check_pwconv(B, K, M, P, "pwconv_stream_plan")) return rc;
+    if (!out || x_align_bytes < 0 || y_align_bytes < 0) return fail(CABINET_ERR_INVALID_ARG, "pwconv_stream_plan: null out / negative alignment");
+    cabinet::pwconv_stream_plan_query(B, M, K, P, (unsigned)x_align_bytes, (unsigned)y_align_bytes, out);
+    return CABINET_OK;
+}
+
 int cabinet_pwconv_fwd(const float* x, const float* w, int B, int Ci, int Co, int P, float* y, cabinet_stream_t stream) {
     if (int rc = check_pwconv(B, Ci, Co, P, "pwconv_fwd")) return rc;
     if (!x || !w || !y) return fail(CABINET_ERR_INVALID_ARG, "pwconv_fwd: null tensor pointer");
@@ -1380,6 +1390,15 @@ static int check_pw_bn(int B, int Ci, int Co, int P, int act, const char* who) {
 
 int cabinet_pw_bn_bwd_supported(int Ci, int Co, int P) {
     return Ci > 0 && Co > 0 && P > 0 && cabinet::pw_bn_bwd_supported(Ci, Co, P) ? 1 : 0;
+}
+
+int cabinet_pw_bn_bwd_plan(int B, int Ci, int Co, int P, int dx_align_bytes, int out[5]) {
+    if (B <= 0 || Ci <= 0 || Co <= 0 || P <= 0 || dx_align_bytes < 0 || !out)
+        return fail(CABINET_ERR_INVALID_ARG, "pw_bn_bwd_plan: non-positive dimension, negative alignment or null out");
+    if (!cabinet::pw_bn_bwd_supported(Ci, Co, P))
+        return fail(CABINET_ERR_UNSUPPORTED, "pw_bn_bwd_plan: Ci=%d, Co=%d, P=%d (multiples of 8, <= 96, P <= 2^21)", Ci, Co, P);
+    cabinet::pw_bn_bwd_plan_query(B, Ci, Co, P, (unsigned)dx_align_bytes, out);
+    return CABINET_OK;
 }
 
 size_t cabinet_pw_bn_act_bwd_workspace_bytes(int B, int Ci, int Co, int P) {
@@ -1436,6 +1455,16 @@ int cabinet_pw_bn_dwconv_bwd(const float* dy, const float* z, const float* x, co
 // ------------------------------------------------------ wide pointwise convolution: weight gradient
 int cabinet_pwconv_wide_supported(int Ci, int Co, int P) {
     return Ci > 0 && Co > 0 && P > 0 && cabinet::pwconv_wide_supported(Ci, Co, P) ? 1 : 0;
+}
+
+int cabinet_pwconv_wide_plan(int B, int Ci, int Co, int P, int out[5]) {
+    if (B <= 0 || Ci <= 0 || Co <= 0 || P <= 0 || !out)
+        return fail(CABINET_ERR_INVALID_ARG, "pwconv_wide_plan: non-positive dimension or null out");
+    if (!cabinet::pwconv_wide_supported(Ci, Co, P))
+        return fail(CABINET_ERR_UNSUPPORTED, "pwconv_wide_plan: Ci=%d, Co=%d, P=%d (multiples of 8, <= 4096, P <= 2^21, max(Ci, Co) * P <= 2^28)",
+                    Ci, Co, P);
+    cabinet::pwconv_wide_plan_query(B, Ci, Co, P, out);
+    return CABINET_OK;
 }
 
 size_t cabinet_pwconv_wide_wgrad_workspace_bytes(int B, int Ci, int Co, int P) {

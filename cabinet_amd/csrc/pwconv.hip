@@ -269,18 +269,53 @@ size_t pwconv_bwd_workspace(int B, int Ci, int Co, int P) {
 // stores, and 8 KQ NC operand registers; the 16-byte form (NC = 4) is taken where these stay within 224, which leaves two
 // waves on every SIMD (one-wave workgroups, 8 on a CU); the 8-byte form has no such limit among the supported shapes.
 static constexpr bool stream_vec4_fits(int mb, int kq) { return 4 * (32 * mb + 8 * kq) <= 224; }
-static int stream_vec(int mb, int kq, const float* x, const float* y, int P) {
-    const uintptr_t at = reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(y);
+static int stream_vec(int mb, int kq, uintptr_t x_at, uintptr_t y_at, int P) {  // the addresses, or their residues modulo 16
+    const uintptr_t at = x_at | y_at;
     if (P % 4 == 0 && at % 16 == 0 && stream_vec4_fits(mb, kq)) return 4;
     if (P % 2 == 0 && at % 8 == 0) return 2;
     return 1;
 }
 
+// Where the pipelined form measured no faster than the plain one at a routed shape (tools/time_pwconv.py, DESIGN.md K10):
+//   64 x 24 (dx of 64 -> 24)              48.4 - 48.9 us against 47.9 - 49.5 at 8 x 256^2
+//   24 x 72 (dx of 24 -> 72, 72 -> 24)    34.1 - 35.2 us against 33.4 - 34.4 at 2 x 512 x 256, where a wave walks 2 blocks
+//                                         (at 8 x 256^2, 4 blocks: 48.7 - 50.9 against 54.5 - 55.7)
+// Only these two walk lengths, 2 and 4 blocks per wave, were measured: the threshold between them (plain up to 2 blocks) is
+// where config 5 sits, the crossover at other plane sizes is unmeasured.
+static bool stream_plain(int mb, int kq, int nblocks64) {
+    if (mb == 2 && kq == 2) return true;
+    if (mb == 1 && kq == 5) return nblocks64 <= 2 * PW_GRID;
+    return false;
+}
+
+// What stream_launch does with an M x K product on B planes of P pixels: the one place where it is decided (the launch below
+// and the plan query of the C ABI both read it).  The grid is min(nblocks, 256 x resident workgroups): that figure is the
+// runtime's and not part of the plan.
+struct StreamPlan {
+    int pipelined, v, px, bpi, nblocks;  // plain form: v = 1 (dword accesses), 64-pixel blocks
+};
+static StreamPlan stream_plan(int B, int M, int K, int P, uintptr_t x_at, uintptr_t y_at) {
+    const int mb = blocks_of(M), kq = ceil_div(K, 16);
+    StreamPlan pl{};
+    pl.pipelined = stream_plain(mb, kq, B * ceil_div(P, 64)) ? 0 : 1;
+    pl.v = pl.pipelined ? stream_vec(mb, kq, x_at, y_at, P) : 1;
+    pl.px = pl.v == 4 ? 128 : 64;
+    pl.bpi = ceil_div(P, pl.px);
+    pl.nblocks = B * pl.bpi;
+    return pl;
+}
+
+void pwconv_stream_plan_query(int B, int M, int K, int P, unsigned x_align, unsigned y_align, int out[4]) {
+    const StreamPlan pl = stream_plan(B, M, K, P, x_align, y_align);
+    out[0] = pl.pipelined, out[1] = pl.v, out[2] = pl.px, out[3] = pl.nblocks;
+}
+
 template <int MB, int KQ, int V>
-static hipError_t stream_launch_v(const float* a, int sm, int sk, int M, int K, const float* x, int B, int P, float* y,
-                                  hipStream_t stream) {
+static hipError_t stream_launch_v(const StreamPlan& pl, const float* a, int sm, int sk, int M, int K, const float* x, int P,
+                                  float* y, hipStream_t stream) {
     if constexpr ((V != 4 || stream_vec4_fits(MB, KQ)) && MB * ((KQ + 1) / 2) <= 8) {
-        const int bpi = ceil_div(P, V == 4 ? 128 : 64), nblocks = B * bpi;
+        if (pl.px != 32 * (V == 1 ? 2 : V)) return hipErrorInvalidValue;  // the kernel's block is the plan's
+        const int bpi = pl.bpi, nblocks = pl.nblocks;
         const size_t lds = (size_t)32 * MB * (K + 1) * sizeof(float);
         // every launched workgroup is resident: as many one-wave workgroups on a CU as the instantiation's registers and
         // its largest A tile (K = 16 KQ) admit, 8 at the most (two waves on a SIMD).  Asked of the runtime once per device
@@ -309,18 +344,18 @@ static hipError_t stream_launch_v(const float* a, int sm, int sk, int M, int K, 
 }
 
 template <int MB, int KQ>
-static hipError_t stream_launch_kq(int v, const float* a, int sm, int sk, int M, int K, const float* x, int B, int P,
+static hipError_t stream_launch_kq(const StreamPlan& pl, const float* a, int sm, int sk, int M, int K, const float* x, int P,
                                    float* y, hipStream_t stream) {
-    if (v == 4) return stream_launch_v<MB, KQ, 4>(a, sm, sk, M, K, x, B, P, y, stream);
-    if (v == 2) return stream_launch_v<MB, KQ, 2>(a, sm, sk, M, K, x, B, P, y, stream);
-    return stream_launch_v<MB, KQ, 1>(a, sm, sk, M, K, x, B, P, y, stream);
+    if (pl.v == 4) return stream_launch_v<MB, KQ, 4>(pl, a, sm, sk, M, K, x, P, y, stream);
+    if (pl.v == 2) return stream_launch_v<MB, KQ, 2>(pl, a, sm, sk, M, K, x, P, y, stream);
+    return stream_launch_v<MB, KQ, 1>(pl, a, sm, sk, M, K, x, P, y, stream);
 }
 
 template <int MB>
-static hipError_t stream_launch_mb(int kq, int v, const float* a, int sm, int sk, int M, int K, const float* x, int B, int P,
-                                   float* y, hipStream_t stream) {
+static hipError_t stream_launch_mb(int kq, const StreamPlan& pl, const float* a, int sm, int sk, int M, int K, const float* x,
+                                   int P, float* y, hipStream_t stream) {
 #define PW_STREAM(KQV) \
-    case KQV: return stream_launch_kq<MB, KQV>(v, a, sm, sk, M, K, x, B, P, y, stream)
+    case KQV: return stream_launch_kq<MB, KQV>(pl, a, sm, sk, M, K, x, P, y, stream)
     switch (kq) {
         PW_STREAM(1);
         PW_STREAM(2);
@@ -334,36 +369,23 @@ static hipError_t stream_launch_mb(int kq, int v, const float* a, int sm, int sk
 #undef PW_STREAM
 }
 
-// Where the pipelined form measured no faster than the plain one at a routed shape (tools/time_pwconv.py, DESIGN.md K10):
-//   64 x 24 (dx of 64 -> 24)              48.4 - 48.9 us against 47.9 - 49.5 at 8 x 256^2
-//   24 x 72 (dx of 24 -> 72, 72 -> 24)    34.1 - 35.2 us against 33.4 - 34.4 at 2 x 512 x 256, where a wave walks 2 blocks
-//                                         (at 8 x 256^2, 4 blocks: 48.7 - 50.9 against 54.5 - 55.7)
-// Only these two walk lengths, 2 and 4 blocks per wave, were measured: the threshold between them (plain up to 2 blocks) is
-// where config 5 sits, the crossover at other plane sizes is unmeasured.
-static bool stream_plain(int mb, int kq, int nblocks64) {
-    if (mb == 2 && kq == 2) return true;
-    if (mb == 1 && kq == 5) return nblocks64 <= 2 * PW_GRID;
-    return false;
-}
-
 static hipError_t stream_launch(const float* a, int sm, int sk, int M, int K, const float* x, int B, int P, float* y,
                                 hipStream_t stream) {
     const int mb = blocks_of(M), kq = ceil_div(K, 16);
-    const int bpi = ceil_div(P, 64), nblocks = B * bpi;
-    if (stream_plain(mb, kq, nblocks)) {
-        const int grid = nblocks < PW_GRID ? nblocks : PW_GRID;
+    const StreamPlan pl = stream_plan(B, M, K, P, reinterpret_cast<uintptr_t>(x), reinterpret_cast<uintptr_t>(y));
+    if (!pl.pipelined) {
+        const int grid = pl.nblocks < PW_GRID ? pl.nblocks : PW_GRID;
         const size_t lds = (size_t)32 * mb * (K + 1) * sizeof(float);
         if (mb == 1)
-            hipLaunchKernelGGL(pw_stream_plain_kernel<1>, dim3(grid), dim3(64), lds, stream, a, sm, sk, M, K, x, P, nblocks, bpi, y);
+            hipLaunchKernelGGL(pw_stream_plain_kernel<1>, dim3(grid), dim3(64), lds, stream, a, sm, sk, M, K, x, P, pl.nblocks, pl.bpi, y);
         else
-            hipLaunchKernelGGL(pw_stream_plain_kernel<2>, dim3(grid), dim3(64), lds, stream, a, sm, sk, M, K, x, P, nblocks, bpi, y);
+            hipLaunchKernelGGL(pw_stream_plain_kernel<2>, dim3(grid), dim3(64), lds, stream, a, sm, sk, M, K, x, P, pl.nblocks, pl.bpi, y);
         return hipGetLastError();
     }
-    const int v = stream_vec(mb, kq, x, y, P);
-    if (mb == 1) return stream_launch_mb<1>(kq, v, a, sm, sk, M, K, x, B, P, y, stream);
-    if (mb == 2) return stream_launch_mb<2>(kq, v, a, sm, sk, M, K, x, B, P, y, stream);
-    if (mb == 3) return stream_launch_mb<3>(kq, v, a, sm, sk, M, K, x, B, P, y, stream);
-    return stream_launch_mb<4>(kq, v, a, sm, sk, M, K, x, B, P, y, stream);
+    if (mb == 1) return stream_launch_mb<1>(kq, pl, a, sm, sk, M, K, x, P, y, stream);
+    if (mb == 2) return stream_launch_mb<2>(kq, pl, a, sm, sk, M, K, x, P, y, stream);
+    if (mb == 3) return stream_launch_mb<3>(kq, pl, a, sm, sk, M, K, x, P, y, stream);
+    return stream_launch_mb<4>(kq, pl, a, sm, sk, M, K, x, P, y, stream);
 }
 
 hipError_t pwconv_fwd_run(const float* x, const float* w, int B, int Ci, int Co, int P, float* y, hipStream_t stream) {

@@ -165,6 +165,11 @@ bool pwconv_wide_supported(int Ci, int Co, int P) {
            (size_t)(Ci > Co ? Ci : Co) * P <= ((size_t)1 << 28);
 }
 
+void pwconv_wide_plan_query(int B, int Ci, int Co, int P, int out[5]) {
+    const PwwPlan pl = pww_plan(B, Ci, Co, P);
+    out[0] = pl.bm, out[1] = pl.bn, out[2] = pl.tiles_m, out[3] = pl.tiles_n, out[4] = pl.nsplit;
+}
+
 size_t pwconv_wide_wgrad_workspace(int B, int Ci, int Co, int P) {
     return align_up((size_t)pww_plan(B, Ci, Co, P).nsplit * Co * Ci * sizeof(float), 256);
 }
@@ -368,6 +373,27 @@ static PwwPlan pw_bn_plan(int B, int Ci, int Co, int P) {
     return pl;
 }
 
+// the launch: the plan above, the store form of dx (16 bytes where the plane and the pointer allow; a null dx counts as aligned)
+// and the LDS of the instantiation -- read by pw_bn_bwd_run and by the plan query of the C ABI
+struct PwBnLaunch {
+    PwwPlan pl;
+    int vec;
+    size_t lds;
+};
+static PwBnLaunch pw_bn_launch(int B, int Ci, int Co, int P, uintptr_t dx_at) {
+    PwBnLaunch l{};
+    l.pl = pw_bn_plan(B, Ci, Co, P);
+    l.vec = (P % 4 == 0 && dx_at % 16 == 0) ? 1 : 0;
+    l.lds = ((size_t)32 * (l.pl.bm + l.pl.bn) * PWW_LD + (size_t)32 * l.pl.bm * (32 * l.pl.bn + 4) + (size_t)32 * l.pl.bm * 8) *
+            sizeof(float);
+    return l;
+}
+
+void pw_bn_bwd_plan_query(int B, int Ci, int Co, int P, unsigned dx_align, int out[5]) {
+    const PwBnLaunch l = pw_bn_launch(B, Ci, Co, P, dx_align);
+    out[0] = l.pl.bm, out[1] = l.pl.bn, out[2] = l.pl.nsplit, out[3] = l.vec, out[4] = (int)l.lds;
+}
+
 bool pw_bn_bwd_supported(int Ci, int Co, int P) {
     return Ci <= 96 && Co <= 96 && pwconv_wide_supported(Ci, Co, P);
 }
@@ -381,11 +407,11 @@ hipError_t pw_bn_bwd_run(const float* g, const float* z, const float* x, const f
                          const float* gamma, const float* beta, const float* coef, int B, int Ci, int Co, int P, int act,
                          float* dx, float* dw, void* slab_ws, hipStream_t stream) {
     if (!dx && !dw) return hipSuccess;
-    const PwwPlan pl = pw_bn_plan(B, Ci, Co, P);
-    const size_t lds = ((size_t)32 * (pl.bm + pl.bn) * PWW_LD + (size_t)32 * pl.bm * (32 * pl.bn + 4) + (size_t)32 * pl.bm * 8) *
-                       sizeof(float);
+    const PwBnLaunch launch = pw_bn_launch(B, Ci, Co, P, reinterpret_cast<uintptr_t>(dx));
+    const PwwPlan& pl = launch.pl;
+    const size_t lds = launch.lds;
     float* slabs = dw ? static_cast<float*>(slab_ws) : nullptr;
-    const int vec = (P % 4 == 0 && reinterpret_cast<uintptr_t>(dx) % 16 == 0) ? 1 : 0;
+    const int vec = launch.vec;
     hipError_t e = hipSuccess;
 #define PWB(BMV, BNV)                                                                                                    \
     {                                                                                                                    \

@@ -596,6 +596,12 @@ int cabinet_stem_conv_bn_bwd(const float* g, const float* z, const float* x, con
  *   bwd: dx = W^T dy (skipped if NULL), dw = sum_{b,p} dy (x) x (skipped if NULL); ordered slab sum, deterministic.
  * ------------------------------------------------------------------------- */
 int cabinet_pwconv_supported(int Ci, int Co, int P);
+/* The launch plan of the stream kernel for one M x K product (forward: M = Co, K = Ci; input gradient: M = Ci, K = Co) on B
+ * planes of P pixels -- the decision cabinet_pwconv_fwd / _bwd take, read from the same function; host-only, no HIP call.
+ * x_align_bytes / y_align_bytes: the operand's and the output's address modulo 16 (or, what decides the same, its alignment
+ * 16, 8 or 4).  out = {form (0 plain walk, 1 pipelined), pixels per lane and access V (4, 2, 1), pixels per block, blocks}.
+ * The grid is min(blocks, 256 x the workgroups the runtime reports resident on a CU, 8 at the most). */
+int cabinet_pwconv_stream_plan(int B, int M, int K, int P, int x_align_bytes, int y_align_bytes, int out[4]);
 int cabinet_pwconv_fwd(const float* x, const float* w, int B, int Ci, int Co, int P, float* y, cabinet_stream_t stream);
 size_t cabinet_pwconv_bwd_workspace_bytes(int B, int Ci, int Co, int P);
 int cabinet_pwconv_bwd(const float* dy, const float* x, const float* w, int B, int Ci, int Co, int P,
@@ -614,6 +620,10 @@ int cabinet_pwconv_bwd(const float* dy, const float* x, const float* w, int B, i
  *       dbn_weight, dbn_bias are bit for bit cabinet_bn_dwconv_bwd's.  x (B,Ci,H,W), pw_weight (C,Ci).
  * ------------------------------------------------------------------------- */
 int cabinet_pw_bn_bwd_supported(int Ci, int Co, int P);
+/* The launch plan of the BN form, as the two entry points below take it (host-only, no HIP call).  dx_align_bytes: the address
+ * of dx modulo 16 (0 for a NULL dx).  out = {row blocks of Co (BM), row blocks of Ci (BN), splits = workgroups, 16-byte dx
+ * stores (1) or dwords (0), dynamic LDS bytes}. */
+int cabinet_pw_bn_bwd_plan(int B, int Ci, int Co, int P, int dx_align_bytes, int out[5]);
 size_t cabinet_pw_bn_act_bwd_workspace_bytes(int B, int Ci, int Co, int P);
 int cabinet_pw_bn_act_bwd(const float* g, const float* z, const float* x, const float* pw_weight, const float* bn_weight,
                           const float* bn_bias, const float* save_mean, const float* save_invstd, int B, int Ci, int Co, int P,
@@ -636,6 +646,9 @@ int cabinet_pw_bn_dwconv_bwd(const float* dy, const float* z, const float* x, co
  * workspace: cabinet_pwconv_wide_wgrad_workspace_bytes (one (Co,Ci) slab per split of the pixels; at most 512).
  * ------------------------------------------------------------------------- */
 int cabinet_pwconv_wide_supported(int Ci, int Co, int P);
+/* The launch plan of cabinet_pwconv_wide_wgrad (host-only, no HIP call): out = {BM, BN (32-row blocks of Co / Ci per tile),
+ * tiles along Co, tiles along Ci, splits of the pixel chunks}; the grid is tiles x splits, the workspace one slab per split. */
+int cabinet_pwconv_wide_plan(int B, int Ci, int Co, int P, int out[5]);
 size_t cabinet_pwconv_wide_wgrad_workspace_bytes(int B, int Ci, int Co, int P);
 int cabinet_pwconv_wide_wgrad(const float* dy, const float* x, int B, int Ci, int Co, int P, float* dw,
                               void* workspace, size_t workspace_bytes, cabinet_stream_t stream);

@@ -90,7 +90,7 @@ def act_inputs(B, Ci, Co, P, seed=0, identity=False):
     """-> dict of CPU fp32 tensors: x (B,Ci,P), w (Co,Ci), z = W x (rounded), g, gamma, beta, mean, invstd."""
     gen = torch.Generator().manual_seed(1000 * seed + 7 * Ci + 13 * Co + P + B)
     x = torch.randn(B, Ci, P, generator=gen)
-    w = torch.eye(Co) if identity else torch.randn(Co, Ci, generator=gen) / Ci ** 0.5
+    w = torch.eye(Co, Ci) if identity else torch.randn(Co, Ci, generator=gen) / Ci ** 0.5
     z = _on_boundary(torch.einsum("oi,bip->bop", w, x) * 0.5 + 0.5)
     g = torch.randn(B, Co, P, generator=gen)
     gamma, beta, mean, invstd = _params(Co, gen)
